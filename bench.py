@@ -1,6 +1,12 @@
 """bench.py — decoded tokens/s of int8 greedy decode on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline JSON line; with
+--dump-outputs DIR it also writes what the last timed step computed (DIR/ids.npy, the
+[batch, max_len] decoded ids in global sentence order, float32: ids < 2^24 are exact there);
+the inputs are seeded, so two builds can be compared output for output.  --full adds
+every side measurement and check listed below.
 
 One "step" = one whole greedy decode of one batch of synthetic sentences: encoder, cross
 K/V, max_len-1 = 71 KV-cached decoder steps, generator + argmax (the fixed loop of
@@ -9,10 +15,13 @@ config 2: batch 32 per GPU, source length <= 64 padded to 72.  For N > 1 one glo
 (batch x N sentences, or --global-batch, e.g. 2048 for BASELINE config 5) is partitioned
 by source length over the ranks (one process per GPU, torchrun), each decoding its shard
 with its own weight replica: no collective on the data path; RCCL carries
-the barrier, the max-over-ranks of the elapsed time and, after the timed region, the
-all-gather of the ids that rank 0 checks against a re-decoded sample.
+the barrier, the max-over-ranks of the elapsed time and, after the timed region (with
+--full or --dump-outputs), the all-gather of the ids, which rank 0 checks against a
+re-decoded sample (--full) or writes out (--dump-outputs).
 
-Printed JSON (rank 0) adds:
+With --full the printed JSON (rank 0) adds:
+  ids_verified_vs_single_batch_sample, public_api_ms_per_decode, step, cfg4 / cfg5 / cfg1 lines
+  (--no-cfg3 and --no-cpu-baseline leave legs of the --full run out)
   roofline     decode's dominant kernel, algorithmic bytes per launch / profiled avg duration
   roofline_encoder  the cfg3 encoder's FFN1 launch against the int8 MFMA peak (+ PMC traffic)
   cpu_baseline oracle/torch_port.py (the reference's fp32 fake-quant arithmetic in torch)
@@ -503,8 +512,13 @@ def main():
     ap.add_argument("--src-len", type=int, default=72)
     ap.add_argument("--max-len", type=int, default=72)
     ap.add_argument("--weight-bits", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cfg3", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's decoded ids to DIR/ids.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks (roofline, step, public API, "
+                         "cfg1/3/4/5, CPU baseline, id verification)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-cfg3", action="store_true", help="with --full: skip the cfg3/4/5/1 lines")
     args = ap.parse_args()
 
     import torch
@@ -570,15 +584,25 @@ def main():
     tokens = G * (L - 1) * args.steps
     value = tokens / dt
 
-    # after the timed region: gather every rank's ids into global order and, on rank 0,
-    # re-decode a sample of sentences from every shard in one batch of its own (per-token
-    # quantization: a sentence's tokens do not depend on its batch)
-    allids = gather_ids(dist, ids.to(coll_dev), idx, G, world) if world > 1 else None
+    # after the timed region (--full or --dump-outputs): gather every rank's ids into global
+    # order; --dump-outputs writes them, and with --full rank 0 re-decodes a sample of
+    # sentences from every shard in one batch of its own (per-token quantization: a
+    # sentence's tokens do not depend on its batch)
+    want_ids = args.full or args.dump_outputs is not None
+    allids = gather_ids(dist, ids.to(coll_dev), idx, G, world) if world > 1 and want_ids else None
     verified = None
-    if rank == 0:
+    if rank == 0 and want_ids:
         if allids is None:
             allids = np.full((G, L), -1, np.int64)
             allids[idx] = ids.cpu().numpy()
+    if rank == 0 and args.dump_outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        rows = allids
+        if rows.size * 4 > 64 << 20:            # a fixed, seeded sample of the sentences
+            keep = np.random.default_rng(0).choice(G, (64 << 20) // (4 * L), replace=False)
+            rows = rows[np.sort(keep)]
+        np.save(os.path.join(args.dump_outputs, "ids.npy"), rows.astype(np.float32))
+    if rank == 0 and args.full:
         shards = length_sorted_shards(glens, world)
         pick = np.unique(np.concatenate([sh[[0, len(sh) // 2, -1]] for sh in shards if len(sh)]))
         ref = greedy_decode(model, gsrc[pick], (gsrc[pick] != 2)[:, None, :], L, 0)
@@ -587,7 +611,24 @@ def main():
     def progress(msg):      # stderr, so a long run is visibly alive (stdout: the JSON line only)
         print(f"bench: {msg} ({time.perf_counter() - t_start:.0f} s since start)", file=sys.stderr, flush=True)
 
-    if rank == 0:
+    # the headline: all a plain run prints
+    head = {"metric": "decoded tokens/sec IWSLT14 de-en int8 greedy "
+                      f"(batch {G} over {world} GPU, {L - 1} steps)",
+            "value": value, "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak" if not args.global_batch else "strong",
+            "vs_baseline": None,
+            "dtype": "int8" if args.weight_bits == 8 else "int4w-int8a",
+            "data": "synthetic (seeded src ids, random-init weights of the reference architecture)",
+            "config": {"workload": f"{workload_name(args, G, world)}: greedy decode, src<=64 "
+                                   f"padded to {S}, max_len={L}, {G} sentences length-sorted "
+                                   f"over {world} rank(s)",
+                       "global_batch": G, "per_gpu_batch": B, "seq_len": S,
+                       "parallelism": f"sentence-shard x{world}"}}
+    if rank == 0 and not args.full:
+        print(json.dumps(head))
+    if rank == 0 and args.full:
         progress(f"timed region done: {value:.0f} tokens/s")
         Bd = min(B, 32)
         chain_us, nop_us = time_dominant(Bd)
@@ -629,20 +670,7 @@ def main():
             t0 = time.perf_counter()
             greedy_decode(model, gsrc[idx], (gsrc[idx] != 2)[:, None, :], L, 0)
             pub.append(time.perf_counter() - t0)
-        out = {"metric": "decoded tokens/sec IWSLT14 de-en int8 greedy "
-                         f"(batch {G} over {world} GPU, {L - 1} steps)",
-               "value": value, "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-               "higher_is_better": True,
-               "scaling": "weak" if not args.global_batch else "strong",
-               "vs_baseline": None,
-               "dtype": "int8" if args.weight_bits == 8 else "int4w-int8a",
-               "data": "synthetic (seeded src ids, random-init weights of the reference architecture)",
-               "config": {"workload": f"{workload_name(args, G, world)}: greedy decode, src<=64 "
-                                      f"padded to {S}, max_len={L}, {G} sentences length-sorted "
-                                      f"over {world} rank(s)",
-                          "global_batch": G, "per_gpu_batch": B, "seq_len": S,
-                          "parallelism": f"sentence-shard x{world}"},
+        out = {**head,
                "ids_verified_vs_single_batch_sample": verified,
                "public_api_ms_per_decode": min(pub) * 1e3,
                "roofline": roof, "step": step}

@@ -39,7 +39,9 @@ def pytest_collection_modifyitems(config, items):
 
 @pytest.fixture(scope="session")
 def golden_ops():
-    return dict(np.load(os.path.join(GOLDEN, "golden_ops.npz")))
+    sys.path.insert(0, GOLDEN)
+    from golden_io import load_golden
+    return load_golden("golden_ops")
 
 
 @pytest.fixture(scope="session")

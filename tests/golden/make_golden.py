@@ -123,7 +123,9 @@ def main():
     xg = rng.standard_normal((4, 512)).astype(np.float32)
     out["gen_x"] = xg
     out["gen_ref"] = m.generator(T(xg)).numpy()
-    np.savez_compressed(os.path.join(HERE, "golden_ops.npz"), **out)
+    sys.path.insert(0, HERE)
+    from golden_io import save_golden
+    save_golden("golden_ops", out)
 
     # ---- module level: encoder, decoder, greedy decode ----------------------------------
     Bm, Sm = 2, 16

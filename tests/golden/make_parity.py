@@ -1,4 +1,4 @@
-"""Generate tests/golden/golden_parity.npz: the fixtures of the quantitative reference-parity
+"""Generate tests/golden/golden_parity.partNN.npz: the fixtures of the quantitative reference-parity
 tests (tests/test_parity_quant.py), from the REFERENCE's own modules.
 
 Run in the build container only (it imports /root/reference, which never travels):
@@ -152,7 +152,8 @@ def main():
                dec_ys=dys.numpy(), top8=np.stack(top8, 1), top8_id=np.stack(top8_id, 1))
     out.update({f"enc_q{i:03d}": q for i, q in enumerate(enc_q)})
     out.update({f"dec_q{i:03d}": q for i, q in enumerate(dec_q)})
-    np.savez_compressed(os.path.join(HERE, "golden_parity.npz"), **out)
+    from golden_io import save_golden
+    save_golden("golden_parity", out)
     print({k: v.shape for k, v in out.items()}, "reference:", REF)
 
 

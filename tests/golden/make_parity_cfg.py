@@ -1,4 +1,4 @@
-"""Generate tests/golden/golden_parity_cfg.npz: reference-replay fixtures at the BASELINE
+"""Generate tests/golden/golden_parity_cfg.partNN.npz: reference-replay fixtures at the BASELINE
 shapes (tests/test_parity_cfg.py), from the REFERENCE's own modules.
 
 Run in the build container only (it imports /root/reference, which never travels):
@@ -137,7 +137,8 @@ def main():
     assert np.array_equal(gdouts[-1], gm["dec_out"])
     oracle_pass("gm_dec", qgd, gdouts, lambda c: decoder_chain(om, gm["ys"], gm["memory"], gm["src_mask"], c))
 
-    np.savez_compressed(os.path.join(HERE, "golden_parity_cfg.npz"), **out)
+    from golden_io import save_golden
+    save_golden("golden_parity_cfg", out)
     print({k: v.shape for k, v in out.items() if not k.endswith(("_idx", "_val"))}, "reference:", REF)
 
 

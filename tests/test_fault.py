@@ -37,23 +37,21 @@ def test_matmul_names():
 def test_reference_target_files_map():
     """Every target of the reference's campaign files (QK^T, PV, FFN1, FFN2 per layer)
     maps to the matching (module, layer, target)."""
-    import glob
     import json
     import os
-    d = "/root/reference/input"
-    if not os.path.isdir(d):
-        pytest.skip("reference not mounted")
-    n = 0
-    for mod in ("encoder", "decoder"):
-        for p in glob.glob(f"{d}/{mod}/matmul_*.json"):
-            j = json.load(open(p))
-            kind = j["module"].split("/")[1]          # FirstFC / SecondFC / First|SecondMatMul
-            _, _, lin = F.matmul_target(j["target_layer"], j["module"])
-            want = {"FirstFC": ("FFN1",), "SecondFC": ("FFN2",), "FirstMatMul": ("QK", "CQK"),
-                    "SecondMatMul": ("PV", "CPV")}[kind]
-            assert lin in want, (p, lin)
-            n += 1
-    assert n == 24 + 36
+    # the campaign files' contents, stored as data by tests/golden/make_matmul_targets.py
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                           "matmul_targets.json")) as fh:
+        targets = json.load(fh)
+    n = {"Encoder": 0, "Decoder": 0}
+    for j in targets:
+        mod, kind = j["module"].split("/")[:2]        # FirstFC / SecondFC / First|SecondMatMul
+        _, _, lin = F.matmul_target(j["target_layer"], j["module"])
+        want = {"FirstFC": ("FFN1",), "SecondFC": ("FFN2",), "FirstMatMul": ("QK", "CQK"),
+                "SecondMatMul": ("PV", "CPV")}[kind]
+        assert lin in want, (j, lin)
+        n[mod] += 1
+    assert n == {"Encoder": 24, "Decoder": 36}
 
 
 def test_random_fault_draws():

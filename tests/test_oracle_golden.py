@@ -119,8 +119,9 @@ def test_qexp_accuracy():
 def _replay(prefix):
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    from golden_io import load_golden
     from replay_codes import Codes
-    fx = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_parity_cfg.npz"))
+    fx = load_golden("golden_parity_cfg")
     return sys.modules["replay_codes"], Codes(sparse=Codes.unpack(fx, prefix))
 
 

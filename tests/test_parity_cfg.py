@@ -1,6 +1,6 @@
 """Quantitative reference parity at the BASELINE shapes (cfg3 encoder S=128, cfg2 S=72 with
 the decoder teacher-forced over T=71), from fixtures the reference itself generated
-(tests/golden/make_parity_cfg.py -> golden_parity_cfg.npz).
+(tests/golden/make_parity_cfg.py -> golden_parity_cfg.partNN.npz).
 
 test_parity_quant.py replays the reference's rounding decisions layer by layer on 2 short
 sentences; here the oracle runs each stack end to end (its own embedding, 6 layers, the
@@ -22,6 +22,7 @@ from oracle import qtx_oracle as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
+from golden_io import load_golden  # noqa: E402
 from replay_codes import Codes, decoder_chain, encoder_chain, sample_rows  # noqa: E402
 
 f32 = np.float32
@@ -30,7 +31,7 @@ NOISE_REL = 2e-6
 
 @pytest.fixture(scope="module")
 def fx():
-    return dict(np.load(os.path.join(HERE, "golden", "golden_parity_cfg.npz")))
+    return load_golden("golden_parity_cfg")
 
 
 def _check_pass(fx, name, outs, codes):

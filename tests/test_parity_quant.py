@@ -7,7 +7,7 @@ accumulators and a fixed fp32 order.  The two differ by fp32 roundi
 (~1e-6 relative), and that noise can move a value across a rint tie in a downstream
 quantizer: the only mechanism by which they can differ by more than noise.  These tests
 check exactly that, against fixtures recorded from the reference (tests/golden/
-make_parity.py, golden_parity.npz):
+make_parity.py, golden_parity.partNN.npz):
 
 1. replay: every rounding decision the reference took inside an encoder / decoder pass
    (activation quantizers quant_linear.py:30-43, P quantization attention.py:33-35) is
@@ -20,21 +20,24 @@ make_parity.py, golden_parity.npz):
    oracle then picks one of the reference's runner-ups.
 """
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from oracle import qtx_oracle as O
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+from golden_io import load_golden  # noqa: E402
+
 f32 = np.float32
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_parity.npz")
 TIE_EPS = 1e-3          # |frac(x/s) - 1/2| below this: a near-tie the fp32 noise may flip
 NOISE_REL = 2e-6         # layer-output deviation allowed once the codes are replayed (measured <= 4.4e-7)
 
 
 @pytest.fixture(scope="module")
 def gp():
-    return dict(np.load(GOLDEN))
+    return load_golden("golden_parity")
 
 
 class Replay:

@@ -12,5 +12,5 @@ tail -3 $O/pytest.log
 [ $rc -eq 0 ] || { grep -E "FAIL|Error|assert" $O/pytest.log | head -30; exit $rc; }
 timeout -k 10 150 python tools/stamp_bench.py > $O/stamps.log 2>&1 || { echo stamps failed; tail $O/stamps.log; exit 1; }
 grep dec_attn $O/stamps.log
-timeout -k 10 400 python bench.py --no-cpu-baseline --no-cfg3 > $O/bench.json 2> $O/bench.err || { echo bench failed; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-cfg3 > $O/bench.json 2> $O/bench.err || { echo bench failed; tail -20 $O/bench.err; exit 1; }
 python -c "import json; d=json.load(open('$O/bench.json')); print('tok/s', round(d['value']), 'ms', round(d['ms_per_step'], 3), 'step_us', round(d['step']['us'], 1))"

@@ -1,8 +1,9 @@
 import sys, numpy as np, torch
-sys.path.insert(0, '.'); sys.path.insert(0, 'onnx-transformer_amd')
+sys.path[:0] = ['.', 'onnx-transformer_amd', 'tests/golden']
+from golden_io import load_golden
 from qtx.model import QtxModel
 from qtx.weights import synthetic_state_dict
-g = np.load('tests/golden/golden_ops.npz')
+g = load_golden('golden_ops')
 sd = synthetic_state_dict(20241223, ln_random=True)
 m = QtxModel(sd)
 ids = torch.from_numpy(g['emb_ids']).cuda()
