@@ -30,6 +30,12 @@
  * except qtx_model_create; `stream` is a hipStream_t (0 = default stream); every function
  * returns 0 on success or a non-zero qtx_status, with a message in qtx_last_error().
  * Thread-compatible: one stream per thread; the model handle is read-only after creation.
+ * Alignment: the kernels move rows in 16-byte vectors, so every device buffer must start
+ * 16-byte aligned (any hipMalloc'd base does).  The entry points that take a stride
+ * (qtx_linear_rows: ldo8 / o8_ts; qtx_skinny_linear: ldx; qtx_decode_attention: ldy) check
+ * the base and the stride on the host and return QTX_E_INVALID before anything is launched.
+ * Extents are exact: a call writes nothing outside the output and scratch extents stated
+ * here, and writes every element of them (tests/test_gpu_bounds.py).
  */
 #ifndef QTX_H_
 #define QTX_H_
@@ -260,7 +266,12 @@ int32_t qtx_attention_i8_quant(const int8_t* q, const float* sq, const int8_t* k
  *          + layer_norm.py of the next sublayer)
  *   epi 2  relu(y): per-row absmax of each tile -> pmax_out [N/512][M]
  *   epi 3  relu(y) quantized per token with m = max_p pmax_in[p][M] (p < pmax_n) ->
- *          out8 [M,N] (ld ldo8) + os [M]         (FFN hidden, position_feed_forward.py:12) */
+ *          out8 [M,N] (ld ldo8) + os [M]         (FFN hidden, position_feed_forward.py:12)
+ * Strides (in elements): ldo8 >= 512 (epi 0) / >= N (epi 3), o8_ts >= 0 and os_ts >= 0 are
+ * free — Q, K and V may share one pitched buffer (ldo8 = 1600, o8_ts = 512), the bytes
+ * between the rows and the floats between the scale tiles are never written — but out8 is
+ * stored in 16-byte vectors: out8 16-byte aligned, ldo8 % 16 == 0 (a KP out8: % 64) and
+ * o8_ts % 16 == 0, else QTX_E_INVALID.  A and W must be 16-byte aligned too. */
 typedef struct qtx_row_gemm {
   const int8_t* A; const float* sa; const int8_t* W; const float* sw; const float* bias;
   int32_t M, N, K, epi;
@@ -274,8 +285,10 @@ typedef struct qtx_row_gemm {
    * K % 256 == 0.
    * kp = 2: the weight-stationary kernel (K == 512 only): A in the KP layout, W packed by
    * qtx_pack_w_ws; each workgroup keeps a 512-column slice of W on chip and streams 64-row
-   * blocks of A.  Outputs exactly as kp = 1, except that epi 3's out8 must hold M + (M & 1)
-   * rows (the KP pad row of an odd M is written as scratch).
+   * blocks of A.  Outputs exactly as kp = 1, except for the pad row of an odd M in the KP
+   * outputs (epi 1's lnq, epi 3's out8; both hold M + (M & 1) rows in either layout): kp = 1
+   * leaves it untouched, kp = 2 / 3 write it as scratch (their stores are clipped by a buffer
+   * descriptor, which cannot end between the two interleaved rows of a pair).
    * kp = 3: epi 3 in ONE pass (N == 2048, K == 512, W as for kp = 2): the per-token row
    * maximum is exchanged between the column slices' workgroups inside the launch, so
    * pmax_in / pmax_n are not read; pmax_out is the exchange scratch (>= 32 * M + 2048 bytes,
@@ -340,6 +353,10 @@ int32_t qtx_pack_w_ws(const int8_t* W, int32_t N, int32_t K, int8_t* out, void* 
  * (res), 4 partial row absmax of the output per 16-column tile into pmax_out [N/16][M].
  * N % 16 == 0, K in {512, 2048} (amode 1: K = 512); M * max(ldx, K), M * N and N * K below
  * 2^30 (the kernels address their operands with 32-bit byte offsets), else QTX_E_UNSUPPORTED.
+ * Supported flags: 0, 1, 2 and 1|4 (every other combination: QTX_E_UNSUPPORTED, nothing
+ * written).  X rows are ldx floats apart and read in 16-byte vectors: X (amode 0: A) and W
+ * 16-byte aligned, ldx % 4 == 0, ldx >= K, else QTX_E_INVALID; only the K floats of a row and
+ * the pmax_n * M partial maxima are used.
  * quant_linear.py:111-119, layer_norm.py:12-15. */
 int32_t qtx_skinny_linear(int32_t amode, const int8_t* A, const float* sa, const float* X,
                           int64_t ldx, const float* ln_a, const float* ln_b,
@@ -358,7 +375,11 @@ int32_t qtx_skinny_linear(int32_t amode, const int8_t* A, const float* sa, const
  *   skc/svc [B][kv_bs].  Out: fp32 context ctx [B,512]
  * and the per-head absmax pmax [8][B] (the next GEMM's per-token quantization, amode 2 of
  * qtx_skinny_linear with pmax_n = 8).  Keys <= 128.  The PV MatMul runs in the decoder's
- * canonical order (four partial chains; qtx_attention_i8 with dec = 1). */
+ * canonical order (four partial chains; qtx_attention_i8 with dec = 1).
+ * y rows are ldy floats apart (ldy >= the row width, ldy % 4 == 0; y, kc and vc 16-byte
+ * aligned, else QTX_E_INVALID).  Self: only cache row *step_dev (k, v and both scales) is
+ * written.  Cross: the caches are read only, S <= kv_bs, and rows S .. kv_bs - 1 (and the
+ * pad keys of the last value group) are never used. */
 int32_t qtx_decode_attention(int32_t kv_new, const float* y, int64_t ldy, int8_t* kc,
                              int8_t* vc, float* skc, float* svc, int32_t kv_bs,
                              const int32_t* step_dev, int32_t S, const uint8_t* mask,

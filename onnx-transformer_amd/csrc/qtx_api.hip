@@ -59,6 +59,8 @@ int fail(int code, const char* fmt, ...) {
   } while (0)
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+// a base the kernels' 16-byte vector loads / stores can take (null: not passed)
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // bump allocator over a caller-provided (or model-owned) device region
 struct Arena {
@@ -1958,6 +1960,20 @@ int32_t qtx_linear_rows(const qtx_row_gemm* a, void* stream) {
                   (g.epi == RE_RELU_QUANT_PMAX && g.out8 && g.os &&
                    (g.kp == 3 || g.kp == 5 ? g.pmax_out != nullptr : (g.pmax_in && g.pmax_n > 0)));
   if (!ok) return fail(QTX_E_INVALID, "operands missing for epi %d", g.epi);
+  // A, W and out8 move in 16-byte vectors (k_gemm_row: plain stores; the WS kernels: buffer
+  // stores through a descriptor of M * ldo8 bytes), so their bases and the out8 strides must
+  // be multiples of 16 and a row must hold its tile — checked here, before any launch
+  if (!aligned16(g.A) || !aligned16(g.W))
+    return fail(QTX_E_INVALID, "A / W must be 16-byte aligned");
+  if (g.epi == RE_QUANT || g.epi == RE_RELU_QUANT_PMAX) {
+    const long row = g.epi == RE_QUANT ? 512 : g.N;
+    if (!aligned16(g.out8) || g.ldo8 < row || g.ldo8 % 16 || (g.kp && g.epi != RE_QUANT && g.ldo8 % 64))
+      return fail(QTX_E_INVALID, "out8 must be 16-byte aligned with ldo8 %% 16 == 0 (KP: %% 64) "
+                                 "and ldo8 >= %ld (ldo8=%ld)", row, (long)g.ldo8);
+    if (g.epi == RE_QUANT && (g.o8_ts % 16 || g.o8_ts < 0 || g.os_ts < 0))
+      return fail(QTX_E_INVALID, "o8_ts must be a non-negative multiple of 16, os_ts >= 0 "
+                                 "(o8_ts=%ld os_ts=%ld)", (long)g.o8_ts, (long)g.os_ts);
+  }
   const hipError_t e = g.kp == 3 || g.kp == 5 ? launch_gemm_wsx(g, (hipStream_t)stream)
                        : g.kp == 2 || g.kp == 4 ? launch_gemm_ws(g, (hipStream_t)stream)
                                    : launch_gemm_row(g, (hipStream_t)stream);
@@ -2018,6 +2034,10 @@ int32_t qtx_skinny_linear(int32_t amode, const int8_t* A, const float* sa, const
     return fail(QTX_E_INVALID, "operands missing for amode %d", amode);
   if (((flags & EPI_RESIDUAL) && !res) || ((flags & EPI_ROWMAX) && !pmax_out))
     return fail(QTX_E_INVALID, "flags need res / pmax_out");
+  // the A / X rows and the W fragments are read in 16-byte vectors (8-byte for 4-bit W)
+  if (!aligned16(W) || (amode == A_I8 ? !aligned16(A) : (!aligned16(X) || ldx < K || ldx % 4)))
+    return fail(QTX_E_INVALID, "skinny: A / X / W must be 16-byte aligned, ldx %% 4 == 0 and "
+                               "ldx >= K (ldx=%ld)", (long)ldx);
   SkinnyArgs g{};
   g.amode = amode; g.A = A; g.sa = sa; g.X = X; g.ldx = ldx; g.ln_a = ln_a; g.ln_b = ln_b;
   g.pmax_in = pmax_in; g.pmax_n = pmax_n;
@@ -2040,6 +2060,10 @@ int32_t qtx_decode_attention(int32_t kv_new, const float* y, int64_t ldy, int8_t
   if (kv_new ? (!step_dev || kv_bs <= 0 || kv_bs > 128)
              : (!mask || S <= 0 || S > 128 || S > kv_bs))
     return fail(QTX_E_INVALID, "decode attention: bad step/mask/S/kv_bs");
+  // y rows and the cached key / value rows are read in 16-byte vectors
+  if (!aligned16(y) || !aligned16(kc) || !aligned16(vc) || ldy % 4 || ldy < (kv_new ? 1536 : 512))
+    return fail(QTX_E_INVALID, "decode attention: y / kc / vc must be 16-byte aligned, "
+                               "ldy %% 4 == 0 and ldy >= the row width (ldy=%ld)", (long)ldy);
   DecAttnArgs a{};
   a.y = y; a.ldy = ldy; a.kc = kc; a.vc = vc; a.skc = skc; a.svc = svc; a.kv_bs = kv_bs;
   a.step = step_dev; a.S = S; a.mask = mask; a.kv_new = kv_new;

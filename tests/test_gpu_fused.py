@@ -194,6 +194,7 @@ def test_decode_self_attention(torch, B, step, kv_bs):
     np.testing.assert_array_equal(kcd.cpu().numpy(), kc)       # cache append
     np.testing.assert_array_equal(vungroup4(vcd.cpu().numpy(), kv_bs), vc)
     np.testing.assert_array_equal(skd.cpu().numpy(), skc)
+    np.testing.assert_array_equal(svd.cpu().numpy(), svc)
     n = step + 1
     ctx, _ = O.attention(qq[:, None], sq[:, None], kc[:, :n], skc[:, :n], vc[:, :n],
                          svc[:, :n], np.ones((B, 1, n), np.uint8), dec=True)

@@ -204,8 +204,8 @@ def test_embed(torch, gpu_model, golden_ops, oracle_model):
 @pytest.mark.parametrize("M", [37, 32, 5, 100, 256])
 def test_generator(torch, gpu_model, golden_ops, oracle_model, M):
     """Logits bit-exact (fp32-MFMA chain == the oracle's sequential fma chain), argmax
-    exact, log-probs within the platform log's ulp; M > 32 runs several 16-row blocks per
-    workgroup under one load of the weight strips (ragged last group at M = 37 and 100)."""
+    exact, log-probs within the platform log's ulp; each workgroup runs one 16-row block
+    (ragged last block at M = 37 and 100)."""
     gx = golden_ops["gen_x"]
     x = (np.concatenate([gx] * (M // len(gx) + 1))[:M]
          * np.linspace(0.1, 3, M, dtype=f32)[:, None]).astype(f32)
