@@ -36,6 +36,97 @@ __device__ __forceinline__ uint4 unpack_i4(uint2 h) {
 }
 
 // =====================================================================================
+// Kernel-argument preload.  gfx950 hands a wave the first 14 dwords of its kernel-argument
+// segment in SGPRs at launch (16 user SGPRs less the segment pointer; the build passes
+// -amdgpu-kernarg-preload-count, qtx/_build.py) — but only leading scalar parameters, never
+// a by-value struct, which costs an s_load + s_waitcnt before the first address exists.  The
+// step's kernels are latency-bound, so they take those 14 dwords as seven
+// 64-bit scalars — a "lead" block per prologue mode, holding what the first load phase
+// needs and nothing the instantiation does not read — and everything else as a trailing
+// struct, fetched by s_load while the first loads are in flight.  The launchers pack the
+// blocks from SkinnyArgs / DecAttnArgs; the kernels rebuild the same struct in registers.
+// Pointers travel as integers and come back as global (address space 1) pointers.
+// =====================================================================================
+struct KaLead { uint64_t w[7]; };
+#define QTX_KA_PARAMS uint64_t ka0, uint64_t ka1, uint64_t ka2, uint64_t ka3, uint64_t ka4, \
+                      uint64_t ka5, uint64_t ka6
+#define QTX_KA_VALS KaLead{{ka0, ka1, ka2, ka3, ka4, ka5, ka6}}
+#define QTX_KA_ARGS(l) (l).w[0], (l).w[1], (l).w[2], (l).w[3], (l).w[4], (l).w[5], (l).w[6]
+template <class L> KaLead ka_pack(const L& l) {
+  static_assert(sizeof(L) == sizeof(KaLead), "a lead block is the 14 preloaded dwords");
+  return __builtin_bit_cast(KaLead, l);
+}
+inline uint64_t ka_int(const void* p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); }
+template <class T> __device__ __forceinline__ T* ka_ptr(uint64_t v) {
+  return (T*)(__attribute__((address_space(1))) T*)v;
+}
+
+// The skinny GEMMs' lead blocks (no padding: every byte is a field), roughly in order of first
+// use (all 14 dwords arrive together); strides are 32-bit (launch_skinny bounds every offset
+// by 2^30).  What does not fit — the bias, and for the LayerNorm / partial-maxima prologues the
+// residual — is loaded last in the first load burst, after the wait for SkTail.
+template <int AMODE> struct SkLead;
+template <> struct SkLead<A_I8> {     // (sa is read after the weights are issued: SkTail)
+  uint64_t A; int M, N; uint64_t W; int ldw, ldr; uint64_t sw, bias, res;
+};
+template <> struct SkLead<A_LN> {
+  uint64_t X; int M, ldx; uint64_t ln_a, ln_b, W; int ldw, N; uint64_t sw;
+};
+template <> struct SkLead<A_F32Q> {
+  uint64_t X; int M, ldx; uint64_t pmax_in; int pmax_n, ldw; uint64_t W; int N, ldo; uint64_t sw;
+};
+template <> struct SkLead<A_F32R> {
+  uint64_t X; int M, ldx; uint64_t W; int ldw, N; uint64_t sw, res; int ldr, ldo;
+};
+struct SkTail {   // the epilogue's operands (where a lead block holds one too, the kernel takes that)
+  const float* sa; const float* bias; const float* res; float* out; float* pmax_out;
+  int ldo, ldr;
+};
+
+template <int AMODE> KaLead sk_lead(const SkinnyArgs& g) {
+  SkLead<AMODE> l{};
+  l.M = g.M; l.N = g.N; l.W = ka_int(g.W); l.ldw = (int)g.ldw; l.sw = ka_int(g.sw);
+  if constexpr (AMODE == A_I8) {
+    l.A = ka_int(g.A); l.ldr = (int)g.ldr; l.bias = ka_int(g.bias); l.res = ka_int(g.res);
+  } else {
+    l.X = ka_int(g.X); l.ldx = (int)g.ldx;
+    if constexpr (AMODE == A_LN) { l.ln_a = ka_int(g.ln_a); l.ln_b = ka_int(g.ln_b); }
+    if constexpr (AMODE == A_F32Q) { l.pmax_in = ka_int(g.pmax_in); l.pmax_n = g.pmax_n; l.ldo = (int)g.ldo; }
+    if constexpr (AMODE == A_F32R) { l.res = ka_int(g.res); l.ldr = (int)g.ldr; l.ldo = (int)g.ldo; }
+  }
+  return ka_pack(l);
+}
+inline SkTail sk_tail(const SkinnyArgs& g) {
+  return SkTail{g.sa, g.bias, g.res, g.out, g.pmax_out, (int)g.ldo, (int)g.ldr};
+}
+// the kernel's view: SkinnyArgs again (amode / K / flags are template parameters there)
+template <int AMODE>
+__device__ __forceinline__ SkinnyArgs sk_args(const KaLead& k, const SkTail& t) {
+  const SkLead<AMODE> l = __builtin_bit_cast(SkLead<AMODE>, k);
+  SkinnyArgs g{};
+  g.sa = t.sa; g.bias = t.bias; g.res = t.res; g.out = t.out; g.pmax_out = t.pmax_out;
+  g.ldo = t.ldo; g.ldr = t.ldr;
+  g.M = l.M; g.N = l.N; g.W = ka_ptr<const int8_t>(l.W); g.ldw = l.ldw;
+  g.sw = ka_ptr<const float>(l.sw);
+  if constexpr (AMODE == A_I8) {
+    g.A = ka_ptr<const int8_t>(l.A); g.ldr = l.ldr; g.bias = ka_ptr<const float>(l.bias);
+    g.res = ka_ptr<const float>(l.res);
+  } else {
+    g.X = ka_ptr<const float>(l.X); g.ldx = l.ldx;
+    if constexpr (AMODE == A_LN) { g.ln_a = ka_ptr<const float>(l.ln_a); g.ln_b = ka_ptr<const float>(l.ln_b); }
+    if constexpr (AMODE == A_F32Q) { g.pmax_in = ka_ptr<const float>(l.pmax_in); g.pmax_n = l.pmax_n; g.ldo = l.ldo; }
+    if constexpr (AMODE == A_F32R) { g.res = ka_ptr<const float>(l.res); g.ldr = l.ldr; g.ldo = l.ldo; }
+  }
+  return g;
+}
+// <<<>>> with the blocks unpacked (kernel name last: its template arguments hold commas)
+#define QTX_SK_LAUNCH(AM, grid, block, ...)                                          \
+  do {                                                                               \
+    const KaLead ka_l_ = sk_lead<AM>(g);                                             \
+    __VA_ARGS__<<<grid, block, 0, st>>>(QTX_KA_ARGS(ka_l_), sk_tail(g));             \
+  } while (0)
+
+// =====================================================================================
 // k_skinny
 // =====================================================================================
 // The A operand of a skinny GEMM workgroup (rows m0 .. m0 + RB - 1) into LDS: int8 rows
@@ -165,7 +256,8 @@ __device__ __forceinline__ void skinny_prologue(const SkinnyArgs& g, uint8_t* As
 }
 
 template <int MF, int RB, int K, int WBITS, int AMODE, int FLAGS>
-__global__ __launch_bounds__(256) void k_skinny(SkinnyArgs g) {
+__global__ __launch_bounds__(256) void k_skinny(QTX_KA_PARAMS, SkTail kt) {
+  const SkinnyArgs g = sk_args<AMODE>(QTX_KA_VALS, kt);
   constexpr int BM = 16 * MF;     // MFMA rows (rows >= RB of the A panel are don't-care)
   static_assert(RB % 4 == 0 && RB <= BM, "rows per block");
   constexpr int KW = K / 4;       // K range of one wave
@@ -209,7 +301,9 @@ __global__ __launch_bounds__(256) void k_skinny(SkinnyArgs g) {
     // prologue's own loads count the branch-free path, i.e. wait for the weights too
     const int cc = min(col, g.N - 1);
     swc = ld_at(g.sw, 4u * cc);
-    bc = ld_at(g.bias, 4u * cc);
+    // up to here every address came from preloaded arguments; what follows may wait for the
+    // trailing ones (SkTail), and must not be scheduled above the weights' loads for that
+    __builtin_amdgcn_sched_barrier(0);
     if constexpr (resid) {   // the rows this wave finishes: 4 fg + wave of each tile
 #pragma unroll
       for (int i = 0; i < MF; ++i) {
@@ -217,6 +311,7 @@ __global__ __launch_bounds__(256) void k_skinny(SkinnyArgs g) {
         rv[i] = ld_at(g.res, 4u * (unsigned)(row * (int)g.ldr + cc));
       }
     }
+    bc = ld_at(g.bias, 4u * cc);
   };
 
   // 2. A panel (int8) and per-row scales into LDS
@@ -293,7 +388,8 @@ __global__ __launch_bounds__(256) void k_skinny(SkinnyArgs g) {
 // halves met through LDS — instead of FFN1's per-tile partial maxima.
 // =====================================================================================
 template <bool OWN>
-__global__ __launch_bounds__(512) void k_skinny8_ffn2(SkinnyArgs g) {
+__global__ __launch_bounds__(512) void k_skinny8_ffn2(QTX_KA_PARAMS, SkTail kt) {
+  const SkinnyArgs g = sk_args<OWN ? A_F32R : A_F32Q>(QTX_KA_VALS, kt);
   constexpr int K = 2048, RB = 4, KW = K / 8, NS = KW / 64, LDA = K + 16;
   __shared__ __attribute__((aligned(16))) uint8_t As[16 * LDA];
   __shared__ float sas[16];
@@ -321,9 +417,11 @@ __global__ __launch_bounds__(512) void k_skinny8_ffn2(SkinnyArgs g) {
     wf[s] = ld_at(reinterpret_cast<const uint4*>(g.W), (unsigned)(n * (int)g.ldw + wave * KW + 64 * s + 16 * fg));
   const int col = n0 + fr, cc = min(col, g.N - 1);
   const bool cok = col < g.N;
-  const float swc = ld_at(g.sw, 4u * cc), bc = ld_at(g.bias, 4u * cc);
+  const float swc = ld_at(g.sw, 4u * cc);
+  __builtin_amdgcn_sched_barrier(0);   // as in k_skinny: trailing arguments from here on
   // the epilogue's output of this lane (wave 0): row m0 + (lane >> 4), column n0 + (lane & 15)
   const float rv = ld_at(g.res, 4u * (unsigned)(min(m0 + fg, g.M - 1) * (int)g.ldr + cc));
+  const float bc = ld_at(g.bias, 4u * cc);
   // 3. per-token quantization of the half row into LDS
   {
     const bool ok = m0 + r < g.M;
@@ -388,7 +486,8 @@ __global__ __launch_bounds__(512) void k_skinny8_ffn2(SkinnyArgs g) {
 // epilogue arithmetic: bit-identical to k_skinny.
 // =====================================================================================
 template <int RB, int WBITS, int AMODE, int FLAGS>
-__global__ __launch_bounds__(256) void k_skinny_wide(SkinnyArgs g) {
+__global__ __launch_bounds__(256) void k_skinny_wide(QTX_KA_PARAMS, SkTail kt) {
+  const SkinnyArgs g = sk_args<AMODE>(QTX_KA_VALS, kt);
   constexpr int K = 512, NS = K / 64, LDA = K + 16;
   static_assert(RB % 4 == 0 && RB <= 16, "rows per block");
   __shared__ __attribute__((aligned(16))) uint8_t As[16 * LDA];
@@ -424,6 +523,7 @@ __global__ __launch_bounds__(256) void k_skinny_wide(SkinnyArgs g) {
 #endif
     }
     swc = cok ? ld_at(g.sw, 4u * col) : 0.0f;
+    __builtin_amdgcn_sched_barrier(0);   // as in k_skinny: trailing arguments from here on
     bc = cok ? ld_at(g.bias, 4u * col) : 0.0f;
     if constexpr (RB == 4) {   // the epilogue's one output per lane: row m0 + fg
       rv[0] = (resid && cok && m0 + fg < g.M) ? ld_at(g.res, 4u * (unsigned)((m0 + fg) * (int)g.ldr + col)) : 0.0f;
@@ -539,11 +639,11 @@ template <int RB, int WB, int AM>
 hipError_t skinny_wide_flags(const SkinnyArgs& g, hipStream_t st) {
   const dim3 grid(g.N / 64, (g.M + RB - 1) / RB);
   switch (g.flags) {
-    case 0: k_skinny_wide<RB, WB, AM, 0><<<grid, 256, 0, st>>>(g); break;
-    case EPI_RELU: k_skinny_wide<RB, WB, AM, EPI_RELU><<<grid, 256, 0, st>>>(g); break;
-    case EPI_RESIDUAL: k_skinny_wide<RB, WB, AM, EPI_RESIDUAL><<<grid, 256, 0, st>>>(g); break;
+    case 0: QTX_SK_LAUNCH(AM, grid, 256, k_skinny_wide<RB, WB, AM, 0>); break;
+    case EPI_RELU: QTX_SK_LAUNCH(AM, grid, 256, k_skinny_wide<RB, WB, AM, EPI_RELU>); break;
+    case EPI_RESIDUAL: QTX_SK_LAUNCH(AM, grid, 256, k_skinny_wide<RB, WB, AM, EPI_RESIDUAL>); break;
     case EPI_RELU | EPI_ROWMAX:
-      k_skinny_wide<RB, WB, AM, EPI_RELU | EPI_ROWMAX><<<grid, 256, 0, st>>>(g);
+      QTX_SK_LAUNCH(AM, grid, 256, k_skinny_wide<RB, WB, AM, EPI_RELU | EPI_ROWMAX>);
       break;
     default: return hipErrorInvalidValue;
   }
@@ -570,11 +670,11 @@ template <int MF, int RB, int K, int WB, int AM>
 hipError_t skinny_flags(const SkinnyArgs& g, hipStream_t st) {
   const dim3 grid(g.N / 16, (g.M + RB - 1) / RB);
   switch (g.flags) {
-    case 0: k_skinny<MF, RB, K, WB, AM, 0><<<grid, 256, 0, st>>>(g); break;
-    case EPI_RELU: k_skinny<MF, RB, K, WB, AM, EPI_RELU><<<grid, 256, 0, st>>>(g); break;
-    case EPI_RESIDUAL: k_skinny<MF, RB, K, WB, AM, EPI_RESIDUAL><<<grid, 256, 0, st>>>(g); break;
+    case 0: QTX_SK_LAUNCH(AM, grid, 256, k_skinny<MF, RB, K, WB, AM, 0>); break;
+    case EPI_RELU: QTX_SK_LAUNCH(AM, grid, 256, k_skinny<MF, RB, K, WB, AM, EPI_RELU>); break;
+    case EPI_RESIDUAL: QTX_SK_LAUNCH(AM, grid, 256, k_skinny<MF, RB, K, WB, AM, EPI_RESIDUAL>); break;
     case EPI_RELU | EPI_ROWMAX:
-      k_skinny<MF, RB, K, WB, AM, EPI_RELU | EPI_ROWMAX><<<grid, 256, 0, st>>>(g);
+      QTX_SK_LAUNCH(AM, grid, 256, k_skinny<MF, RB, K, WB, AM, EPI_RELU | EPI_ROWMAX>);
       break;
     default: return hipErrorInvalidValue;
   }
@@ -632,9 +732,9 @@ hipError_t skinny_mode(const SkinnyArgs& g, hipStream_t st) {
     if (g.M <= sk8_maxm && WB == 8 && g.flags == EPI_RESIDUAL &&
         ((g.amode == A_F32Q && g.pmax_n <= 128) || g.amode == A_F32R)) {
       if (g.amode == A_F32R)
-        k_skinny8_ffn2<true><<<dim3(g.N / 16, (g.M + 3) / 4), 512, 0, st>>>(g);
+        QTX_SK_LAUNCH(A_F32R, dim3(g.N / 16, (g.M + 3) / 4), 512, k_skinny8_ffn2<true>);
       else
-        k_skinny8_ffn2<false><<<dim3(g.N / 16, (g.M + 3) / 4), 512, 0, st>>>(g);
+        QTX_SK_LAUNCH(A_F32Q, dim3(g.N / 16, (g.M + 3) / 4), 512, k_skinny8_ffn2<false>);
       return hipGetLastError();
     }
     const int rb_i8 = kn.rb_i8_2048 > 0 ? kn.rb_i8_2048 : (big ? 16 : 4);
@@ -677,8 +777,41 @@ hipError_t launch_skinny(const SkinnyArgs& g, int wbits, hipStream_t st) {
 constexpr int DEC_MAXK = 128;
 constexpr int DEC_KST = 20;   // staged key row stride in dwords
 
+// The lead blocks of k_dec_attn (kernel-argument preload, above): what the loads of phase 0
+// need.  Self: the device position counter (read only by a step replayed at several
+// positions, and by no load's address) stays in the tail; cross: the mask pointer does —
+// its bytes are the phase's last loads, issued when the tail has long arrived.
+template <bool KV_NEW> struct DaLead;
+template <> struct DaLead<true> {
+  uint64_t y; int ldy, kv_bs; uint64_t kc, vc, skc, svc; int host_step1, zero;
+};
+template <> struct DaLead<false> {
+  uint64_t y; int ldy, kv_bs; uint64_t kc, vc, skc, svc; int S, zero;
+};
+struct DaTail { const int* step; const uint8_t* mask; float* ctx; float* pmax; int B; };
+
+template <bool KV_NEW> KaLead da_lead(const DecAttnArgs& a) {
+  DaLead<KV_NEW> l{};
+  l.y = ka_int(a.y); l.ldy = (int)a.ldy; l.kv_bs = (int)a.kv_bs;
+  l.kc = ka_int(a.kc); l.vc = ka_int(a.vc); l.skc = ka_int(a.skc); l.svc = ka_int(a.svc);
+  if constexpr (KV_NEW) l.host_step1 = a.host_step1; else l.S = a.S;
+  return ka_pack(l);
+}
+template <bool KV_NEW>
+__device__ __forceinline__ DecAttnArgs da_args(const KaLead& k, const DaTail& t) {
+  const DaLead<KV_NEW> l = __builtin_bit_cast(DaLead<KV_NEW>, k);
+  DecAttnArgs a{};
+  a.y = ka_ptr<const float>(l.y); a.ldy = l.ldy; a.kv_bs = l.kv_bs;
+  a.kc = ka_ptr<int8_t>(l.kc); a.vc = ka_ptr<int8_t>(l.vc);
+  a.skc = ka_ptr<float>(l.skc); a.svc = ka_ptr<float>(l.svc);
+  if constexpr (KV_NEW) a.host_step1 = l.host_step1; else a.S = l.S;
+  a.step = t.step; a.mask = t.mask; a.ctx = t.ctx; a.pmax = t.pmax; a.B = t.B;
+  return a;
+}
+
 template <bool KV_NEW, int NIT>
-__global__ __launch_bounds__(64) void k_dec_attn(DecAttnArgs a) {
+__global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
+  const DecAttnArgs a = da_args<KV_NEW>(QTX_KA_VALS, kt);
   __shared__ __attribute__((aligned(16))) uint32_t Ks[DEC_MAXK * DEC_KST];   // key rows of this head
   // values of this head, 4-key groups: dword g * 64 + d = keys 4g .. 4g + 3 of dim d
   __shared__ __attribute__((aligned(16))) uint8_t Vs[DEC_MAXK * 64];
@@ -688,10 +821,6 @@ __global__ __launch_bounds__(64) void k_dec_attn(DecAttnArgs a) {
   const int b = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
   QTX_STAMP(0);
   const float* yr = a.y + (long)b * a.ldy;
-  // rows staged (self: rows 0 .. the position when the host passes it, else all allocated)
-  const int nrows = KV_NEW ? (a.host_step1 > 0 ? a.host_step1 : (int)a.kv_bs) : a.S;
-  const long kvb = (long)b * a.kv_bs;
-  const long vgb = (long)b * ((a.kv_bs + 3) >> 2);     // the sentence's first value group
 
   // phase 0: every global load first (one memory latency): this step's q (k, v) rows
   // first — vmcnt retires in issue order, so their quantization (phase 1) then runs while
@@ -709,8 +838,13 @@ __global__ __launch_bounds__(64) void k_dec_attn(DecAttnArgs a) {
   const float q_own = yr[h * 64 + lane];
   const float k_own = KV_NEW ? yr[512 + h * 64 + lane] : 0.0f;
   const float v_own = KV_NEW ? yr[1024 + h * 64 + lane] : 0.0f;
-  // clamped: a stale position (a counter not reset) must not index past the cache
-  const int step = !KV_NEW ? 0 : a.host_step1 > 0 ? a.host_step1 - 1 : min(max(*a.step, 0), (int)a.kv_bs - 1);
+  // (the y row's loads go out before the scalar arithmetic of the cache rows' bases: left to
+  // itself the scheduler puts all of that, ~40 scalar instructions, ahead of the first load)
+  __builtin_amdgcn_sched_barrier(0);
+  // rows staged (self: rows 0 .. the position when the host passes it, else all allocated)
+  const int nrows = KV_NEW ? (a.host_step1 > 0 ? a.host_step1 : (int)a.kv_bs) : a.S;
+  const long kvb = (long)b * a.kv_bs;
+  const long vgb = (long)b * ((a.kv_bs + 3) >> 2);     // the sentence's first value group
   const int rsub = lane >> 2, ch = lane & 3;
   // values: per 16 keys, 4 groups x this head's 64 dims x 4 B = 1 KB, lane = group
   // 4 i + lane / 16, dims 4 (lane % 16) .. + 3
@@ -741,6 +875,10 @@ __global__ __launch_bounds__(64) void k_dec_attn(DecAttnArgs a) {
     keep0 = mb[(unsigned)j0] != 0;
     keep1 = mb[(unsigned)j1] != 0;
   }
+  // the position (no load's address depends on it: read after they are issued; the counter's
+  // pointer comes with the trailing arguments).  Clamped: a stale position (a counter not
+  // reset) must not index past the cache
+  const int step = !KV_NEW ? 0 : a.host_step1 > 0 ? a.host_step1 - 1 : min(max(*a.step, 0), (int)a.kv_bs - 1);
   // cross: keys past the sentence's last unmasked one contribute exactly nothing (score
   // -1e9 -> qexp 0 -> P 0, and fma(0, v, acc) == acc), so the key loops stop there; a
   // fully masked row keeps all S keys (the reference's uniform softmax over -1e9 scores)
@@ -914,15 +1052,17 @@ __global__ __launch_bounds__(64) void k_dec_attn(DecAttnArgs a) {
 template <bool KV_NEW>
 hipError_t dec_attn_nit(const DecAttnArgs& a, int B, int nrows, hipStream_t st) {
   const dim3 grid(B, 8), block(64);
+  const KaLead l = da_lead<KV_NEW>(a);
+  const DaTail t{a.step, a.mask, a.ctx, a.pmax, a.B};
   switch ((nrows + 15) / 16) {
-    case 1: k_dec_attn<KV_NEW, 1><<<grid, block, 0, st>>>(a); break;
-    case 2: k_dec_attn<KV_NEW, 2><<<grid, block, 0, st>>>(a); break;
-    case 3: k_dec_attn<KV_NEW, 3><<<grid, block, 0, st>>>(a); break;
-    case 4: k_dec_attn<KV_NEW, 4><<<grid, block, 0, st>>>(a); break;
-    case 5: k_dec_attn<KV_NEW, 5><<<grid, block, 0, st>>>(a); break;
-    case 6: k_dec_attn<KV_NEW, 6><<<grid, block, 0, st>>>(a); break;
-    case 7: k_dec_attn<KV_NEW, 7><<<grid, block, 0, st>>>(a); break;
-    case 8: k_dec_attn<KV_NEW, 8><<<grid, block, 0, st>>>(a); break;
+    case 1: k_dec_attn<KV_NEW, 1><<<grid, block, 0, st>>>(QTX_KA_ARGS(l), t); break;
+    case 2: k_dec_attn<KV_NEW, 2><<<grid, block, 0, st>>>(QTX_KA_ARGS(l), t); break;
+    case 3: k_dec_attn<KV_NEW, 3><<<grid, block, 0, st>>>(QTX_KA_ARGS(l), t); break;
+    case 4: k_dec_attn<KV_NEW, 4><<<grid, block, 0, st>>>(QTX_KA_ARGS(l), t); break;
+    case 5: k_dec_attn<KV_NEW, 5><<<grid, block, 0, st>>>(QTX_KA_ARGS(l), t); break;
+    case 6: k_dec_attn<KV_NEW, 6><<<grid, block, 0, st>>>(QTX_KA_ARGS(l), t); break;
+    case 7: k_dec_attn<KV_NEW, 7><<<grid, block, 0, st>>>(QTX_KA_ARGS(l), t); break;
+    case 8: k_dec_attn<KV_NEW, 8><<<grid, block, 0, st>>>(QTX_KA_ARGS(l), t); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -931,6 +1071,7 @@ hipError_t dec_attn_nit(const DecAttnArgs& a, int B, int nrows, hipStream_t st) 
 hipError_t launch_dec_attn(const DecAttnArgs& a, int B, hipStream_t st) {
   if (B <= 0) return hipSuccess;
   if (!a.ctx || a.B != B) return hipErrorInvalidValue;
+  if (a.ldy < 0 || a.ldy >= (1L << 31) || a.kv_bs >= (1L << 31)) return hipErrorInvalidValue;   // 32-bit in the lead block
   if (a.kv_new) {
     if (a.kv_bs <= 0 || a.kv_bs > DEC_MAXK || a.host_step1 < 0 || a.host_step1 > a.kv_bs)
       return hipErrorInvalidValue;
@@ -1030,10 +1171,11 @@ hipError_t launch_quant_h2048(const float* X, long ldx, int M, int8_t* q, float*
 // =====================================================================================
 constexpr int GEN_Q = 32;   // float4 groups of 4 k-steps per lane (K = 512)
 
-__global__ __launch_bounds__(1024) void k_generator_mfma(const float* x, long ldx, int M,
-                                                         const float* ln_a, const float* ln_b,
-                                                         const float* Wm, const float* bias,
-                                                         int V, float* logits) {
+// (parameters in order of first use: all but `logits` arrive preloaded in SGPRs)
+__global__ __launch_bounds__(1024) void k_generator_mfma(const float* Wm, int V, int M,
+                                                         const float* bias, const float* x,
+                                                         long ldx, const float* ln_a,
+                                                         const float* ln_b, float* logits) {
   __shared__ __attribute__((aligned(16))) float X[16][514];   // stride 514: conflict-free reads
   __shared__ __attribute__((aligned(16))) v4f part[3][4][64];  // quarters 1..3: [strip][lane]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1106,7 +1248,7 @@ hipError_t launch_generator_mfma(const float* x, long ldx, int M, const float* l
   if ((long)M * V >= (1L << 30) || (long)M * ldx >= (1L << 30)) return hipErrorInvalidValue;   // 32-bit offsets
   const int ngroup = (V + 63) / 64, nrb = (M + 15) / 16;
   const unsigned grid = 8u * nrb * ((ngroup + 7) / 8);
-  k_generator_mfma<<<dim3(grid), dim3(1024), 0, st>>>(x, ldx, M, ln_a, ln_b, Wm, b, V, logits);
+  k_generator_mfma<<<dim3(grid), dim3(1024), 0, st>>>(Wm, V, M, b, x, ldx, ln_a, ln_b, logits);
   return hipGetLastError();
 }
 
@@ -1183,22 +1325,27 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
 // host_s1: the position + 1 when the host knows it (then no read of *step and no step
 // advance: nothing of a decode whose every step knows its position reads the counter);
 // 0: read *step and advance it (the last workgroup to arrive)
-__global__ __launch_bounds__(1024) void k_argmax_embed(const float* logits, int V, int64_t* ids,
-                                                       long ids_bs, int* step, unsigned* arrive,
-                                                       const float* lut, const float* pe,
-                                                       int max_pos, float* xnext, int host_s1) {
+// (parameters in order of first use: those up to ids_bs arrive preloaded in SGPRs)
+__global__ __launch_bounds__(1024) void k_argmax_embed(const float* logits, int V, int host_s1,
+                                                       int* step, const float* pe,
+                                                       const float* lut, int max_pos,
+                                                       long ids_bs, int64_t* ids,
+                                                       unsigned* arrive, float* xnext) {
   __shared__ float Ev[ARG_MAXV];
   __shared__ float redf[16], lse_s;
   __shared__ int redi[16], redc[16], redb[16];
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   QTX_STAMP(0);
-  const int s = host_s1 > 0 ? host_s1 - 1 : *step;
   const unsigned xo = 4u * (unsigned)(m * V);
-  float4 pe_row = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // position s+1 is known up front
-  if (tid < 128) pe_row = ld_at(reinterpret_cast<const float4*>(pe), 16u * (unsigned)(min(s + 1, max_pos - 1) * 128 + tid));
   float t[ARG_NV];
 #pragma unroll
   for (int i = 0; i < ARG_NV; ++i) t[i] = ld_at(logits, xo + 4u * min(tid + ARG_T * i, V - 1));   // clamped
+  // (the logits go out first: their addresses need preloaded arguments only, the position
+  // may be a scalar load of the device counter)
+  __builtin_amdgcn_sched_barrier(0);
+  const int s = host_s1 > 0 ? host_s1 - 1 : *step;
+  float4 pe_row = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // position s+1 is known up front
+  if (tid < 128) pe_row = ld_at(reinterpret_cast<const float4*>(pe), 16u * (unsigned)(min(s + 1, max_pos - 1) * 128 + tid));
   QTX_STAMP(1);
   // max: order-free; every wave reduces the 16 wave maxima itself (no second barrier);
   // with it the non-finite test: bit 0 = a NaN or +inf, bit 1 = a value above -inf
@@ -1303,8 +1450,8 @@ hipError_t launch_argmax_embed(const float* logits, int M, int V, int64_t* ids, 
                                int max_pos, float* xnext, hipStream_t st, int host_s1) {
   if (M <= 0) return hipSuccess;
   if (V > ARG_MAXV || host_s1 < 0 || (long)M * V >= (1L << 30)) return hipErrorInvalidValue;
-  k_argmax_embed<<<dim3(M), dim3(ARG_T), 0, st>>>(logits, V, ids, ids_bs, step, arrive, lut,
-                                                  pe, max_pos, xnext, host_s1);
+  k_argmax_embed<<<dim3(M), dim3(ARG_T), 0, st>>>(logits, V, host_s1, step, pe, lut, max_pos,
+                                                  ids_bs, ids, arrive, xnext);
   return hipGetLastError();
 }
 

@@ -24,6 +24,17 @@ HEADERS = ["qtx_common.h", "qtx_kernels.h", "qtx_ws.h", "qtx_knobs.h"]
 # DESIGN.md §3); HIP keeps correctly rounded fp32 '/' and sqrtf by default.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
          "-ffp-contract=off", "-fno-fast-math", "-Wall"]
+# Per-source flags.  qtx_decode.hip (the decode step's kernels): kernel-argument preload — the
+# leading scalar kernel parameters arrive in SGPRs at wave launch instead of through s_load.
+# 14 dwords is what gfx950 grants (16 user SGPRs less the kernarg segment pointer; a larger
+# count is clamped: .amdhsa_user_sgpr_kernarg_preload_length in the device assembly).
+SOURCE_FLAGS = {"qtx_decode.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"]}
+
+
+def compile_flags(src: str, extra=()) -> list:
+    """The hipcc flags one source is compiled to an object with (tools/build_variant.py and
+    tests/test_kernarg_preload.py use the same)."""
+    return [f for f in FLAGS if f != "-shared"] + SOURCE_FLAGS.get(os.path.basename(src), []) + list(extra)
 
 
 def hipcc() -> str:
@@ -58,11 +69,10 @@ def build(force: bool = False, verbose: bool = False, extra=()) -> str:
         return LIB
     objdir = os.path.join(HERE, "build_obj")
     os.makedirs(objdir, exist_ok=True)
-    cflags = [f for f in FLAGS if f != "-shared"] + list(extra)
 
     def compile_one(src):
         obj = os.path.join(objdir, os.path.splitext(os.path.basename(src))[0] + ("_x" if extra else "") + ".o")
-        cmd = [hipcc(), *cflags, "-c", "-o", obj, os.path.join(CSRC, src)]
+        cmd = [hipcc(), *compile_flags(src, extra), "-c", "-o", obj, os.path.join(CSRC, src)]
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -17,11 +17,10 @@ def main():
     out, extra = os.path.abspath(sys.argv[1]), sys.argv[2:]
     objdir = os.path.join(REPO, "onnx-transformer_amd", "qtx", "build_obj_variant" + os.environ.get("QTX_VARIANT_TAG", ""))
     os.makedirs(objdir, exist_ok=True)
-    cflags = [f for f in _build.FLAGS if f != "-shared"] + extra
 
     def one(src):
         obj = os.path.join(objdir, os.path.splitext(os.path.basename(src))[0] + ".o")
-        r = subprocess.run([_build.hipcc(), *cflags, "-c", "-o", obj, os.path.join(_build.CSRC, src)],
+        r = subprocess.run([_build.hipcc(), *_build.compile_flags(src, extra), "-c", "-o", obj, os.path.join(_build.CSRC, src)],
                            capture_output=True, text=True)
         if r.returncode:
             raise SystemExit(f"{src}: {r.stderr[-3000:]}")
