@@ -16,6 +16,9 @@
  *   qtx_embed            <- model.get_src_embed / get_tgt_embed  encoder_decoder.py:54-58
  *   qtx_generator        <- model.generator(x) + torch.max     generator.py:14-15,
  *                                                            reference/onnx_reference_inference.py:640-641
+ *   qtx_greedy_decode_scored, qtx_generator_top2
+ *                        <- the campaign's torch.topk(prob, 2, dim=1) of a step's generator
+ *                           output           parallelized_inject_onnx_transformer.py:718-740
  *   qtx_row_quant        <- quantize_activation_per_token_absmax / quantize_weight_per_channel_absmax
  *                                                            quant_linear.py:30-43 / :5-17
  *   qtx_layernorm_quant  <- LayerNorm.forward (+ the next W8A8Linear's act quant)
@@ -194,6 +197,48 @@ int32_t qtx_greedy_decode_fault(const qtx_model* m, const int64_t* src,
                                 int64_t start, int64_t* ids, void* ws, size_t ws_bytes,
                                 const qtx_fault* fault, void* stream);
 
+/* ---- scored decode: the two best tokens of every step and their log-probabilities ----
+ * The reference's campaign prints torch.topk(prob, 2, dim=1) of the generator's output at the
+ * step it corrupts (parallelized_inject_onnx_transformer.py:718-740, prob = generator.py:15's
+ * log_softmax): the winner, the runner-up and their margin.  Semantics of every entry point
+ * below, for one logits row x[0..V):
+ *   logp  = the canonical log-softmax: z = x - max, lse = log(lane-split sum of qexp(z)),
+ *           logp = z - lse, bit-identical to oracle/qtx_oracle.py:log_softmax_argmax(x)[0]
+ *           (the log of the denominator is csrc/qtx_common.h:qlog, the oracle host's float32
+ *           log restated operation by operation — not the platform logf).
+ *   top 1 = the first index of the maximum logp: the rule of qtx_greedy_decode, so the token
+ *           the plain decode picks (see the note below on rows the plain tail resolves by logf).
+ *   top 2 = the first index of the maximum logp over v != top 1.
+ *   The selection is on logp, not on the logits: two distinct logits can round to the same
+ *   logp, and then the lower index wins.  "Larger logp, then smaller index" is a total order,
+ *   so the pair does not depend on the order of the reduction.
+ *   Values: logp[top 1], logp[top 2].  They always equal torch.topk(logp, 2).values; the
+ *   indices equal torch.topk's wherever the two values (and the third best) are distinct —
+ *   torch.topk does not promise the first index among equal values.
+ *   A non-finite row (any NaN or +inf, or only -inf) has an all-NaN log-softmax under torch:
+ *   ids (0, 1), both values NaN (the 0 is what the plain decode writes).
+ *   V = tgt_vocab >= 2, else QTX_E_INVALID.
+ * Note: qtx_greedy_decode's tail evaluates lse (with the platform's logf) only for rows with
+ * two logits within 4e-6 of each other; on such a row a 1-ulp difference between logf and
+ * qlog can move a logp collision, so top 1 may then differ from the plain decode's token.
+ * On every other row the two agree by construction (the maximum logit is the unique winner).
+ *
+ * qtx_greedy_decode_fault plus top_ids int64 [B, max_len-1, 2] and top_logp float
+ * [B, max_len-1, 2]: entry t describes the choice of ids[:, t+1], top_ids[:, :, 0] ==
+ * ids[:, 1:].  fault: NULL or an encoder fault.  Same path selection as the plain decode
+ * (fused step with graphs, eager, sub-batches, graphs of several steps, unfused step; the
+ * scored step has its own captured graphs).  The fused step's tail (csrc/qtx_decode.hip
+ * k_top2_embed) needs tgt_vocab <= 8192 and B * tgt_vocab < 2^30, as the plain one.
+ * Writes exactly ids [B, max_len], top_ids and top_logp [B, max_len-1, 2].
+ * ws: qtx_greedy_scored_workspace_size bytes (qtx_greedy_workspace_size is unchanged).
+ * QTX_E_UNSUPPORTED with the diagnostic QTX_DBG_TAIL switch. */
+size_t qtx_greedy_scored_workspace_size(const qtx_model* m, int32_t B, int32_t S,
+                                        int32_t max_len);
+int32_t qtx_greedy_decode_scored(const qtx_model* m, const int64_t* src,
+                                 const uint8_t* src_mask, int32_t B, int32_t S, int32_t max_len,
+                                 int64_t start, int64_t* ids, int64_t* top_ids, float* top_logp,
+                                 void* ws, size_t ws_bytes, const qtx_fault* fault, void* stream);
+
 /* Embeddings + positional encoding: which = 0 (src) / 1 (tgt); ids int64 [B,T] ->
  * out [B,T,d], positions pos0 .. pos0+T-1. */
 int32_t qtx_embed(const qtx_model* m, int32_t which, const int64_t* ids, int32_t B, int32_t T,
@@ -203,6 +248,13 @@ int32_t qtx_embed(const qtx_model* m, int32_t which, const int64_t* ids, int32_t
  * ws: M * tgt_vocab floats. */
 int32_t qtx_generator(const qtx_model* m, const float* x, int32_t M, float* logp,
                       int64_t* ids, void* ws, size_t ws_bytes, void* stream);
+
+/* Generator + torch.topk(prob, 2, dim=1) (generator.py:15,
+ * parallelized_inject_onnx_transformer.py:718-740; semantics: scored decode above):
+ * x [M,d] -> top_ids int64 [M,2], top_logp float [M,2], with no [M,tgt_vocab] log-prob
+ * write.  ws: M * tgt_vocab floats (the raw logits, as qtx_generator).  No vocabulary cap. */
+int32_t qtx_generator_top2(const qtx_model* m, const float* x, int32_t M, int64_t* top_ids,
+                           float* top_logp, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- per-op entry points (parity tests, fault-injection hooks later) ---- */
 
@@ -393,6 +445,16 @@ int32_t qtx_decode_attention(int32_t kv_new, const float* y, int64_t ldy, int8_t
 int32_t qtx_decode_argmax_embed(const qtx_model* m, const float* logits, int32_t M,
                                 int64_t* ids, int64_t ids_bs, int32_t* step_dev,
                                 float* x_next, void* stream);
+
+/* The scored decode step's tail (generator.py:15 + torch.topk(prob, 2, dim=1),
+ * parallelized_inject_onnx_transformer.py:718-740; semantics: scored decode above):
+ * qtx_decode_argmax_embed plus the row's two best (id, logp) into entry [m, s, :] of top_ids
+ * int64 [M, ids_bs-1, 2] and top_logp float [M, ids_bs-1, 2].  Writes exactly ids[m, s+1],
+ * those M entries of top_ids / top_logp, x_next [M, d_model] and the two step words.
+ * 2 <= tgt_vocab <= 8192 and M * tgt_vocab < 2^30, else QTX_E_INVALID / QTX_E_UNSUPPORTED. */
+int32_t qtx_decode_top2_embed(const qtx_model* m, const float* logits, int32_t M, int64_t* ids,
+                              int64_t ids_bs, int64_t* top_ids, float* top_logp,
+                              int32_t* step_dev, float* x_next, void* stream);
 
 /* An empty one-wave kernel on `stream`: the dependent-launch floor that bench.py subtracts
  * from a chain of launches to get per-kernel durations (measurement only, no reference

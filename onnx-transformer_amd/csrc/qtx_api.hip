@@ -1218,6 +1218,10 @@ struct GreedyWS {
   int* gsteps;
   int64_t* ids;       // [B][max_len] the decode writes here; copied out to the caller's ids
   uint8_t* mask;      // [B][S] staged copy of the caller's src_mask
+  // scored decode only (else null): [B][max_len-1][2] the two best ids / log-probs of every
+  // step; copied out to the caller's top_ids / top_logp
+  int64_t* top_ids = nullptr;
+  float* top_logp = nullptr;
 };
 
 // Sub-batch split of the fused decode.  Sentences are independent (per-token quantization:
@@ -1240,7 +1244,9 @@ Groups decode_groups(int B) {
   return Groups{(B + Bg - 1) / Bg, Bg};   // no empty group
 }
 
-GreedyWS carve_greedy(Arena& ar, const qtx_config& c, int B, int S, int max_len) {
+// scored: the scores follow everything else, so the plain layout (and size) is a prefix
+GreedyWS carve_greedy(Arena& ar, const qtx_config& c, int B, int S, int max_len,
+                      bool scored = false) {
   GreedyWS g;
   const int D = c.d_model;
   g.enc = carve_scratch(ar, c, (long)B * S);
@@ -1267,6 +1273,10 @@ GreedyWS carve_greedy(Arena& ar, const qtx_config& c, int B, int S, int max_len)
   g.gsteps = ar.take<int>(4 * QTX_MAX_GROUPS);
   g.ids = ar.take<int64_t>((size_t)B * max_len);
   g.mask = ar.take<uint8_t>((size_t)B * S);
+  if (scored) {
+    g.top_ids = ar.take<int64_t>((size_t)B * (max_len - 1) * 2);
+    g.top_logp = ar.take<float>((size_t)B * (max_len - 1) * 2);
+  }
   return g;
 }
 
@@ -1287,6 +1297,10 @@ GreedyWS group_view(const GreedyWS& g, const qtx_config& c, int i, int b0, int S
   v.pmax_a += (long)8 * b0;               // each sub-batch: its own [P][rows] block
   v.pmax_f += (long)(c.d_ff / 16) * b0;
   v.step = g.gsteps + 4 * i;
+  if (g.top_ids) {
+    v.top_ids += (long)b0 * (max_len - 1) * 2;
+    v.top_logp += (long)b0 * (max_len - 1) * 2;
+  }
   return v;
 }
 
@@ -1417,9 +1431,14 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
   }
   QTX_RUN(256, launch_generator_mfma(s.x, D, B, m->dec_norm[0], m->dec_norm[1], m->gen_wt,
                                      m->gen_b, c.tgt_vocab, g.logits, st));
-  QTX_RUN(256, launch_argmax_embed(g.logits, B, c.tgt_vocab, ids, max_len, g.step,
-                                   reinterpret_cast<unsigned*>(g.step + 1), m->tgt_lut, m->pe,
-                                   c.max_len, s.x, st, host_pos ? t_host + 1 : 0));
+  if (g.top_ids)   // scored decode: the tail that also writes the step's two best (id, logp)
+    QTX_RUN(256, launch_top2_embed(g.logits, B, c.tgt_vocab, ids, max_len, g.top_ids, g.top_logp,
+                                   g.step, reinterpret_cast<unsigned*>(g.step + 1), m->tgt_lut,
+                                   m->pe, c.max_len, s.x, st, host_pos ? t_host + 1 : 0));
+  else
+    QTX_RUN(256, launch_argmax_embed(g.logits, B, c.tgt_vocab, ids, max_len, g.step,
+                                     reinterpret_cast<unsigned*>(g.step + 1), m->tgt_lut, m->pe,
+                                     c.max_len, s.x, st, host_pos ? t_host + 1 : 0));
   return QTX_OK;
 #undef QTX_RUN
 #undef QTX_RUNRC
@@ -1456,8 +1475,12 @@ int greedy_step_unfused(const qtx_model* m, GreedyWS& g, int B, int S, int max_l
   }
   RC(ln_out(s.x, B, m->dec_norm, D, g.xo, st));
   HIPCHK(launch_generator(g.xo, D, B, m->gen_w, m->gen_b, c.tgt_vocab, g.logits, st));
-  HIPCHK(launch_logsoftmax_argmax(g.logits, B, c.tgt_vocab, nullptr, ids, max_len, g.step, 1,
-                                  st));
+  if (g.top_ids)
+    HIPCHK(launch_logsoftmax_top2(g.logits, B, c.tgt_vocab, ids, max_len, g.step, 1, g.top_ids,
+                                  g.top_logp, max_len - 1, st));
+  else
+    HIPCHK(launch_logsoftmax_argmax(g.logits, B, c.tgt_vocab, nullptr, ids, max_len, g.step, 1,
+                                    st));
   HIPCHK(launch_step_inc(g.step, st));
   return QTX_OK;
 }
@@ -1480,6 +1503,13 @@ size_t qtx_greedy_workspace_size(const qtx_model* m, int32_t B, int32_t S, int32
   if (!m) return 0;
   Arena ar;
   carve_greedy(ar, m->cfg, B, S, max_len);
+  return align_up(ar.used);
+}
+size_t qtx_greedy_scored_workspace_size(const qtx_model* m, int32_t B, int32_t S,
+                                        int32_t max_len) {
+  if (!m || max_len < 1) return 0;
+  Arena ar;
+  carve_greedy(ar, m->cfg, B, S, max_len, true);
   return align_up(ar.used);
 }
 
@@ -1649,16 +1679,39 @@ int32_t qtx_generator(const qtx_model* m, const float* x, int32_t M, float* logp
   return QTX_OK;
 }
 
-int32_t qtx_greedy_decode_fault(const qtx_model* m, const int64_t* src,
-                                const uint8_t* src_mask, int32_t B, int32_t S, int32_t max_len,
-                                int64_t start, int64_t* ids, void* ws, size_t ws_bytes,
-                                const qtx_fault* f, void* stream) {
-  if (!m || !src || !src_mask || !ids || !ws) return fail(QTX_E_INVALID, "null argument");
+int32_t qtx_generator_top2(const qtx_model* m, const float* x, int32_t M, int64_t* top_ids,
+                           float* top_logp, void* ws, size_t ws_bytes, void* stream) {
+  if (!m || !x || !top_ids || !top_logp || !ws) return fail(QTX_E_INVALID, "null argument");
+  const int V = m->cfg.tgt_vocab;
+  if (V < 2) return fail(QTX_E_INVALID, "top 2 needs tgt_vocab >= 2 (%d)", V);
+  if (M <= 0) return QTX_OK;
+  if (ws_bytes < (size_t)M * V * sizeof(float)) return fail(QTX_E_WORKSPACE, "ws too small");
+  hipStream_t st = (hipStream_t)stream;
+  float* logits = (float*)ws;   // the raw logits stay in ws[0 .. M*V) for the caller
+  HIPCHK(launch_generator_mfma(x, m->cfg.d_model, M, nullptr, nullptr, m->gen_wt, m->gen_b, V,
+                               logits, st));
+  HIPCHK(launch_logsoftmax_top2(logits, M, V, nullptr, 0, nullptr, 0, top_ids, top_logp, 1, st));
+  return QTX_OK;
+}
+
+// the plain (scored = false: top_ids / top_logp unused) and the scored greedy decode
+static int32_t greedy_decode(const qtx_model* m, const int64_t* src, const uint8_t* src_mask,
+                             int32_t B, int32_t S, int32_t max_len, int64_t start, int64_t* ids,
+                             bool scored, int64_t* top_ids, float* top_logp, void* ws,
+                             size_t ws_bytes, const qtx_fault* f, void* stream) {
+  if (!m || !src || !src_mask || !ids || !ws ||
+      (scored && max_len > 1 && (!top_ids || !top_logp)))   // (max_len 1: no step, no entry)
+    return fail(QTX_E_INVALID, "null argument");
   const qtx_config& c = m->cfg;
   if (B <= 0 || S <= 0 || S > 512 || max_len < 1 || max_len > 512 || max_len > c.max_len ||
       S > c.max_len)
     return fail(QTX_E_INVALID, "bad shape B=%d S=%d max_len=%d", B, S, max_len);
-  if (ws_bytes < qtx_greedy_workspace_size(m, B, S, max_len))
+  if (scored && c.tgt_vocab < 2)
+    return fail(QTX_E_INVALID, "scored decode needs tgt_vocab >= 2 (%d)", c.tgt_vocab);
+  if (scored && knobs().dbg_tail)
+    return fail(QTX_E_UNSUPPORTED, "scored decode: not with QTX_DBG_TAIL");
+  if (ws_bytes < (scored ? qtx_greedy_scored_workspace_size(m, B, S, max_len)
+                         : qtx_greedy_workspace_size(m, B, S, max_len)))
     return fail(QTX_E_WORKSPACE, "workspace too small");
   if (f && f->kind != QTX_FAULT_NONE && f->module != 0)
     return fail(QTX_E_UNSUPPORTED, "greedy decode takes encoder faults (decoder faults: "
@@ -1669,7 +1722,7 @@ int32_t qtx_greedy_decode_fault(const qtx_model* m, const int64_t* src,
   ar.base = (uint8_t*)ws; ar.cap = ws_bytes;
   unsigned* cst = nullptr;
   RC(call_status_begin(m, &cst, st));
-  GreedyWS g = carve_greedy(ar, c, B, S, max_len);
+  GreedyWS g = carve_greedy(ar, c, B, S, max_len, scored);
   g.enc.status = cst;
   // the decode reads the workspace's copy of src_mask and writes the workspace's ids
   // (the captured graphs then depend on the workspace only); ids go out at the end
@@ -1677,7 +1730,28 @@ int32_t qtx_greedy_decode_fault(const qtx_model* m, const int64_t* src,
   RC(greedy_run(m, g, src, B, S, max_len, start, f, st));
   HIPCHK(hipMemcpyAsync(ids, g.ids, (size_t)B * max_len * sizeof(int64_t),
                         hipMemcpyDeviceToDevice, st));
+  if (scored && max_len > 1) {   // the scores likewise
+    const size_t n = (size_t)B * (max_len - 1) * 2;
+    HIPCHK(hipMemcpyAsync(top_ids, g.top_ids, n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(top_logp, g.top_logp, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
   return QTX_OK;
+}
+
+int32_t qtx_greedy_decode_fault(const qtx_model* m, const int64_t* src,
+                                const uint8_t* src_mask, int32_t B, int32_t S, int32_t max_len,
+                                int64_t start, int64_t* ids, void* ws, size_t ws_bytes,
+                                const qtx_fault* f, void* stream) {
+  return greedy_decode(m, src, src_mask, B, S, max_len, start, ids, false, nullptr, nullptr, ws,
+                       ws_bytes, f, stream);
+}
+
+int32_t qtx_greedy_decode_scored(const qtx_model* m, const int64_t* src,
+                                 const uint8_t* src_mask, int32_t B, int32_t S, int32_t max_len,
+                                 int64_t start, int64_t* ids, int64_t* top_ids, float* top_logp,
+                                 void* ws, size_t ws_bytes, const qtx_fault* f, void* stream) {
+  return greedy_decode(m, src, src_mask, B, S, max_len, start, ids, true, top_ids, top_logp, ws,
+                       ws_bytes, f, stream);
 }
 
 int32_t qtx_model_check(const qtx_model* m, void* stream) {
@@ -1793,7 +1867,8 @@ int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S
   // QTX_SKINNY_WIDE, QTX_RB_*, ... pick launch shapes inside the captured step too)
   const std::string variant = std::to_string(knobs_generation()) + ":" + std::to_string(kn.split_ln) +
                               std::to_string(kn.ffn_qkernel) + std::to_string(kn.group_graph) +
-                              std::to_string(kn.device_step);
+                              std::to_string(kn.device_step) +
+                              (g.top_ids ? "s" : "");   // the scored step: an entry of its own
   const GraphKey key{B, S, max_len, gr.G * 1000 + per_graph, g.gsteps, variant};
   auto it = mm->graphs.find(key);
   if (it == mm->graphs.end()) {
@@ -2087,6 +2162,23 @@ int32_t qtx_decode_argmax_embed(const qtx_model* m, const float* logits, int32_t
                                            reinterpret_cast<unsigned*>(step_dev + 1),
                                            m->tgt_lut, m->pe, c.max_len, x_next,
                                            (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(QTX_E_UNSUPPORTED, "tgt_vocab %d", c.tgt_vocab);
+  HIPCHK(e);
+  return QTX_OK;
+}
+
+int32_t qtx_decode_top2_embed(const qtx_model* m, const float* logits, int32_t M, int64_t* ids,
+                              int64_t ids_bs, int64_t* top_ids, float* top_logp,
+                              int32_t* step_dev, float* x_next, void* stream) {
+  if (!m || !logits || !ids || !top_ids || !top_logp || !step_dev || !x_next)
+    return fail(QTX_E_INVALID, "null argument");
+  const qtx_config& c = m->cfg;
+  if (c.tgt_vocab < 2) return fail(QTX_E_INVALID, "top 2 needs tgt_vocab >= 2 (%d)", c.tgt_vocab);
+  if (M <= 0) return QTX_OK;
+  const hipError_t e = launch_top2_embed(logits, M, c.tgt_vocab, ids, ids_bs, top_ids, top_logp,
+                                         step_dev, reinterpret_cast<unsigned*>(step_dev + 1),
+                                         m->tgt_lut, m->pe, c.max_len, x_next,
+                                         (hipStream_t)stream);
   if (e == hipErrorInvalidValue) return fail(QTX_E_UNSUPPORTED, "tgt_vocab %d", c.tgt_vocab);
   HIPCHK(e);
   return QTX_OK;

@@ -165,6 +165,42 @@ __device__ __forceinline__ int wave_max_i32(int v) {
              max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
 
+// ---------------------------------------------------------------- top-2 selection
+// The two best (value, index) entries under the total order "larger value, then smaller
+// index" (torch.max's first-index rule, applied twice).  Entries of one selection have
+// distinct indices, so the order is strict and any merge order gives the same pair.  The
+// empty slot is (-inf, INT_MAX): it loses against every entry, a -inf value included.
+struct Top2 {
+  float v1 = -__builtin_inff(), v2 = -__builtin_inff();
+  int i1 = 0x7fffffff, i2 = 0x7fffffff;
+  static __device__ __forceinline__ bool before(float a, int ia, float b, int ib) {
+    return a > b || (a == b && ia < ib);
+  }
+  __device__ __forceinline__ void add(float v, int i) {
+    if (before(v, i, v1, i1)) { v2 = v1; i2 = i1; v1 = v; i1 = i; }
+    else if (before(v, i, v2, i2)) { v2 = v; i2 = i; }
+  }
+  // merge with the pair of a disjoint set
+  __device__ __forceinline__ void merge(float ov1, int oi1, float ov2, int oi2) {
+    if (before(ov1, oi1, v1, i1)) {         // the other side's best leads: mine or its second follows
+      const bool mine = before(v1, i1, ov2, oi2);
+      v2 = mine ? v1 : ov2; i2 = mine ? i1 : oi2;
+      v1 = ov1; i1 = oi1;
+    } else if (before(ov1, oi1, v2, i2)) {
+      v2 = ov1; i2 = oi1;
+    }
+  }
+};
+// every lane gets the pair of the whole wave (xor butterfly: the two sides are disjoint)
+__device__ __forceinline__ void wave_top2(Top2& t) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const float ov1 = __shfl_xor(t.v1, off, 64), ov2 = __shfl_xor(t.v2, off, 64);
+    const int oi1 = __shfl_xor(t.i1, off, 64), oi2 = __shfl_xor(t.i2, off, 64);
+    t.merge(ov1, oi1, ov2, oi2);
+  }
+}
+
 // ---------------------------------------------------------------- canonical exp
 // qexp(): Cody-Waite reduction + degree-7 Taylor in Horner form with fma (7 fused steps
 // instead of 14 separate ones).  Identical to oracle/qtx_oracle.py:qexp (its fma32 is the
@@ -188,6 +224,35 @@ __device__ __forceinline__ float qexp(float x) {
   p = fmaf(p, r, 1.0f);
   const float e = ldexpf(p, (int)n);
   return x < -80.0f ? 0.0f : e;
+}
+
+// ---------------------------------------------------------------- canonical log
+// qlog(): the float32 log the oracle's log_softmax_argmax takes of the denominator (NumPy's
+// SIMD float32 log, which is not the correctly rounded one: up to 3 ulp from it): x = m * 2^e
+// with m in (sqrt(1/2), sqrt(2)], y = m - 1, log x = fma(e, ln2, P(y) / Q(y)) with P and Q of
+// degree 5 in Horner form with fma and a correctly rounded division.  For normal finite
+// x > 0 (a log-softmax denominator lies in [1, V]).  The scored decode's log-probabilities go
+// out to the caller, so they use this instead of the platform's logf (1 ulp, unspecified
+// rounding): tests/test_scored_abi.py pins a line-by-line mirror of it against the oracle's log.
+__device__ __forceinline__ float qlog(float x) {
+  const uint32_t b = __float_as_uint(x);
+  float m = __uint_as_float((b & 0x007fffffu) | 0x3f000000u);   // [0.5, 1)
+  int e = (int)(b >> 23) - 126;
+  if (m <= 0x1.6a09e6p-1f) { m = m * 2.0f; e -= 1; }
+  const float y = m - 1.0f;
+  float p = 0x1.a8579ap-6f;
+  p = fmaf(p, y, 0x1.860666p-2f);
+  p = fmaf(p, y, 0x1.7ae152p+0f);
+  p = fmaf(p, y, 0x1.0e6c38p+1f);
+  p = fmaf(p, y, 1.0f);
+  p = fmaf(p, y, 0.0f);
+  float q = 0x1.8107bep-8f;
+  q = fmaf(q, y, 0x1.3cb7e6p-3f);
+  q = fmaf(q, y, 0x1.f915c8p-1f);
+  q = fmaf(q, y, 0x1.39fc1ap+1f);
+  q = fmaf(q, y, 0x1.4e6c38p+1f);
+  q = fmaf(q, y, 1.0f);
+  return fmaf((float)e, 0x1.62e43p-1f, p / q);
 }
 
 // ---------------------------------------------------------------- shared-divisor division

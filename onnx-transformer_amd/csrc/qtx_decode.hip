@@ -11,6 +11,8 @@
 //                   generator.py:14-15, decoder.py:16
 //   k_argmax_embed  log_softmax + first argmax + next-token embedding + step advance
 //                   onnx_reference_inference.py:632,640-643
+//   k_top2_embed    its scored form: the two best (id, logp) of the row as well
+//                   parallelized_inject_onnx_transformer.py:718-740
 //
 // All float steps follow the canonical order shared with oracle/qtx_oracle.py.
 #include <cstdlib>
@@ -1452,6 +1454,126 @@ hipError_t launch_argmax_embed(const float* logits, int M, int V, int64_t* ids, 
   if (V > ARG_MAXV || host_s1 < 0 || (long)M * V >= (1L << 30)) return hipErrorInvalidValue;
   k_argmax_embed<<<dim3(M), dim3(ARG_T), 0, st>>>(logits, V, host_s1, step, pe, lut, max_pos,
                                                   ids_bs, ids, arrive, xnext);
+  return hipGetLastError();
+}
+
+// =====================================================================================
+// k_top2_embed: k_argmax_embed's scored form (the campaign's torch.topk(prob, 2) of the
+// step, parallelized_inject_onnx_transformer.py:718-740).  Same workgroup shape, loads and
+// position / arrival-counter contract; it always evaluates the canonical log-softmax
+// (k_argmax_embed's near-tie branch, with the denominator's log taken by qlog: the values
+// go out to the caller) and selects the two best entries of logp under "larger logp, then
+// smaller index" (include/qtx.h: scored decode): per thread, per wave, then over the 16
+// waves.  Row m writes ids[m * ids_bs + s + 1] = top 1, entry (m * (ids_bs - 1) + s) of
+// top_ids / top_logp [.., 2], and the next decoder input tgt_embed(top 1) at position s + 1,
+// bit-identical to k_argmax_embed's.  A non-finite row: ids (0, 1), both values NaN.
+// Limits as k_argmax_embed: V <= ARG_MAXV, M * V < 2^30; and V >= 2.
+// (parameters in order of first use: those up to ids_bs arrive preloaded in SGPRs)
+// =====================================================================================
+__global__ __launch_bounds__(1024) void k_top2_embed(const float* logits, int V, int host_s1,
+                                                     int* step, const float* pe,
+                                                     const float* lut, int max_pos,
+                                                     long ids_bs, int64_t* ids,
+                                                     int64_t* top_ids, float* top_logp,
+                                                     unsigned* arrive, float* xnext) {
+  __shared__ float Ev[ARG_MAXV];
+  __shared__ float redf[16], lse_s, rv1[16], rv2[16];
+  __shared__ int redb[16], ri1[16], ri2[16];
+  const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const unsigned xo = 4u * (unsigned)(m * V);
+  float t[ARG_NV];
+#pragma unroll
+  for (int i = 0; i < ARG_NV; ++i) t[i] = ld_at(logits, xo + 4u * min(tid + ARG_T * i, V - 1));   // clamped
+  __builtin_amdgcn_sched_barrier(0);
+  const int s = host_s1 > 0 ? host_s1 - 1 : *step;
+  float4 pe_row = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (tid < 128) pe_row = ld_at(reinterpret_cast<const float4*>(pe), 16u * (unsigned)(min(s + 1, max_pos - 1) * 128 + tid));
+  // max and the non-finite test, as k_argmax_embed
+  float lm = -3.0e38f;
+  bool nonfin = false, fin = false;
+#pragma unroll
+  for (int i = 0; i < ARG_NV; ++i)
+    if (tid + ARG_T * i < V) {
+      lm = fmaxf(lm, t[i]);
+      nonfin |= !(t[i] < __builtin_inff());
+      fin |= t[i] > -__builtin_inff();
+    }
+  lm = wave_max(lm);
+  const int flags = (__ballot(nonfin) ? 1 : 0) | (__ballot(fin) ? 2 : 0);
+  if (lane == 0) { redf[w] = lm; redb[w] = flags; }
+  __syncthreads();
+  const float mx = wave_max(lane < 16 ? redf[lane] : -3.0e38f);
+  const bool bad = __ballot(lane < 16 && (redb[lane] & 1)) != 0ull ||
+                   __ballot(lane < 16 && (redb[lane] & 2)) == 0ull;
+  Top2 top;
+  if (bad) {                               // an all-NaN log_softmax row (block-uniform)
+    top.i1 = 0; top.i2 = 1;
+    top.v1 = top.v2 = __builtin_nanf("");
+  } else {
+    // e_v = qexp(x_v - max) into LDS for the ordered sum
+#pragma unroll
+    for (int i = 0; i < ARG_NV; ++i) {
+      const int v = tid + ARG_T * i;
+      if (v < V) Ev[v] = qexp(t[i] - mx);
+    }
+    __syncthreads();
+    // canonical denominator: lane l sums e[l], e[l+64], ... in order (one wave), then tree
+    if (w == 0) {
+      float ls = 0.0f;
+#pragma unroll 8
+      for (int v = lane; v < V; v += 64) ls = ls + Ev[v];
+      ls = wave_sum(ls);
+      if (lane == 0) lse_s = qlog(ls);
+    }
+    __syncthreads();
+    const float lse = lse_s;
+    // the two best of logp = (x - max) - lse: this thread's (ascending indices), the wave's
+#pragma unroll
+    for (int i = 0; i < ARG_NV; ++i) {
+      const int v = tid + ARG_T * i;
+      if (v < V) top.add((t[i] - mx) - lse, v);
+    }
+    wave_top2(top);
+    if (lane == 0) { rv1[w] = top.v1; ri1[w] = top.i1; rv2[w] = top.v2; ri2[w] = top.i2; }
+    __syncthreads();
+    // the 16 waves' pairs: every wave merges them itself
+    top = Top2{};
+    if (lane < 16) { top.v1 = rv1[lane]; top.i1 = ri1[lane]; top.v2 = rv2[lane]; top.i2 = ri2[lane]; }
+    wave_top2(top);
+  }
+  const int id = min(max(top.i1, 0), V - 1);   // keeps the embedding gather in bounds, whatever
+  if (tid == 0 && s >= 0 && s + 1 < ids_bs) {  // bounded (stale position)
+    ids[m * ids_bs + s + 1] = id;
+    const long e = 2 * (m * (ids_bs - 1) + s);
+    top_ids[e] = id; top_ids[e + 1] = top.i2;
+    top_logp[e] = top.v1; top_logp[e + 1] = top.v2;
+  }
+  // next decoder input: tgt_embed(id) at position s + 1 (embeddings.py:12-13)
+  if (tid < 128) {
+    const float sc = 0x1.6a09e6p+4f;
+    const float4 e = ld_at(reinterpret_cast<const float4*>(lut), 16u * (unsigned)(id * 128 + tid));
+    const float4 q = pe_row;
+    st_at(reinterpret_cast<float4*>(xnext), 16u * (unsigned)(m * 128 + tid),
+          make_float4(e.x * sc + q.x, e.y * sc + q.y, e.z * sc + q.z, e.w * sc + q.w));
+  }
+  // every workgroup has read *step above; the last one to arrive advances it
+  if (host_s1 == 0 && tid == 0) {
+    const unsigned tk = atomicAdd(arrive, 1u);
+    if (tk == gridDim.x - 1) {
+      *step = s + 1;
+      *arrive = 0u;
+    }
+  }
+}
+
+hipError_t launch_top2_embed(const float* logits, int M, int V, int64_t* ids, long ids_bs,
+                             int64_t* top_ids, float* top_logp, int* step, unsigned* arrive,
+                             const float* lut, const float* pe, int max_pos, float* xnext,
+                             hipStream_t st, int host_s1) {
+  if (M <= 0) return hipSuccess;
+  if (V < 2 || V > ARG_MAXV || host_s1 < 0 || (long)M * V >= (1L << 30)) return hipErrorInvalidValue;
+  k_top2_embed<<<dim3(M), dim3(ARG_T), 0, st>>>(logits, V, host_s1, step, pe, lut, max_pos,
+                                                ids_bs, ids, top_ids, top_logp, arrive, xnext);
   return hipGetLastError();
 }
 

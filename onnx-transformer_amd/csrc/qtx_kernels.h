@@ -235,6 +235,12 @@ hipError_t launch_pack_gen(const float* W, int V, float* out, hipStream_t st);
 hipError_t launch_argmax_embed(const float* logits, int M, int V, int64_t* ids, long ids_bs,
                                int* step, unsigned* arrive, const float* lut, const float* pe,
                                int max_pos, float* xnext, hipStream_t st, int host_s1 = 0);
+// the scored tail: as launch_argmax_embed, plus the two best (id, logp) of the row into entry
+// (m * (ids_bs - 1) + *step) of top_ids / top_logp [.., 2]; hipErrorInvalidValue for V < 2
+hipError_t launch_top2_embed(const float* logits, int M, int V, int64_t* ids, long ids_bs,
+                             int64_t* top_ids, float* top_logp, int* step, unsigned* arrive,
+                             const float* lut, const float* pe, int max_pos, float* xnext,
+                             hipStream_t st, int host_s1 = 0);
 hipError_t launch_rows(const RowArgs& a, hipStream_t st);
 hipError_t launch_attention(const AttnArgs& a, hipStream_t st);
 hipError_t launch_embed(const int64_t* ids, long ids_bs, int B, int T, const int* pos_dev,
@@ -245,6 +251,11 @@ hipError_t launch_generator(const float* x, long ldx, int M, const float* W, con
 hipError_t launch_logsoftmax_argmax(const float* logits, int M, int V, float* logp,
                                     int64_t* ids, long ids_bs, const int* col_dev,
                                     int col_add, hipStream_t st);
+// its top-2 form (no logp write): column col = (col_dev ? *col_dev : 0); ids (may be null)
+// [m, col + col_add] = top 1; entry (m * top_bs + col) of top_ids / top_logp [.., 2].  V >= 2.
+hipError_t launch_logsoftmax_top2(const float* logits, int M, int V, int64_t* ids, long ids_bs,
+                                  const int* col_dev, int col_add, int64_t* top_ids,
+                                  float* top_logp, long top_bs, hipStream_t st);
 hipError_t launch_pack_int4(const int8_t* q, int N, int K, uint8_t* packed, hipStream_t st);
 hipError_t launch_u8_from_any(const void* src, int elem_bytes, long n, uint8_t* dst,
                               hipStream_t st);

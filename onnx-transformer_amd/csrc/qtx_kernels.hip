@@ -8,6 +8,7 @@
 //   k_embed         lut[id] * sqrt(512) + pe[pos]                    embeddings.py:12-13
 //   k_generator     fp32 x.W^T + b (sequential fma chain over k)     generator.py:14-15
 //   k_lsm_argmax    log_softmax + first-index argmax                 onnx_reference_inference.py:640-641
+//   k_lsm_top2      log_softmax + the two best (id, logp)            parallelized_inject_onnx_transformer.py:718-740
 //
 // Every float step follows the canonical order of qtx_common.h / oracle/qtx_oracle.py.
 #include <cstdlib>
@@ -516,6 +517,55 @@ hipError_t launch_logsoftmax_argmax(const float* logits, int M, int V, float* lo
                                     int col_add, hipStream_t st) {
   if (M <= 0) return hipSuccess;
   k_lsm_argmax<<<dim3(M), dim3(64), 0, st>>>(logits, V, logp, ids, ids_bs, col_dev, col_add);
+  return hipGetLastError();
+}
+
+// =====================================================================================
+// k_lsm_top2: k_lsm_argmax's scored form (no vocabulary cap, no logp write): the same
+// canonical sums, the denominator's log by qlog (the values go out to the caller), and the
+// two best entries of logp under "larger logp, then smaller index" (include/qtx.h: scored
+// decode).  A non-finite row: ids (0, 1), both values NaN.  V >= 2.
+// =====================================================================================
+__global__ __launch_bounds__(64) void k_lsm_top2(const float* logits, int V, int64_t* ids,
+                                                 long ids_bs, const int* col_dev, int col_add,
+                                                 int64_t* top_ids, float* top_logp, long top_bs) {
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const float* x = logits + (long)m * V;
+  float lm = -3.0e38f;
+  bool nonfin = false, fin = false;
+  for (int v = lane; v < V; v += 64) {
+    lm = fmaxf(lm, x[v]);
+    nonfin |= !(x[v] < __builtin_inff());
+    fin |= x[v] > -__builtin_inff();
+  }
+  Top2 top;
+  if (__ballot(nonfin) != 0ull || __ballot(fin) == 0ull) {     // wave-uniform
+    top.i1 = 0; top.i2 = 1;
+    top.v1 = top.v2 = __builtin_nanf("");
+  } else {
+    const float mx = wave_max(lm);
+    float ls = 0.0f;
+    for (int v = lane; v < V; v += 64) ls = ls + qexp(x[v] - mx);
+    const float lse = qlog(wave_sum(ls));
+    for (int v = lane; v < V; v += 64) top.add((x[v] - mx) - lse, v);
+    wave_top2(top);
+  }
+  if (lane == 0) {
+    const int col = col_dev ? *col_dev : 0;
+    if (ids) ids[m * ids_bs + col + col_add] = top.i1;
+    const long e = 2 * (m * top_bs + col);
+    top_ids[e] = top.i1; top_ids[e + 1] = top.i2;
+    top_logp[e] = top.v1; top_logp[e + 1] = top.v2;
+  }
+}
+
+hipError_t launch_logsoftmax_top2(const float* logits, int M, int V, int64_t* ids, long ids_bs,
+                                  const int* col_dev, int col_add, int64_t* top_ids,
+                                  float* top_logp, long top_bs, hipStream_t st) {
+  if (M <= 0) return hipSuccess;
+  if (V < 2) return hipErrorInvalidValue;
+  k_lsm_top2<<<dim3(M), dim3(64), 0, st>>>(logits, V, ids, ids_bs, col_dev, col_add, top_ids,
+                                           top_logp, top_bs);
   return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@ Public surface mirrors the reference's entry points:
   InferenceSession(path).run(None, feeds)      ~ onnxruntime.InferenceSession
   run_module(module, feeds, ...)               ~ onnx_optimized_inference.run_module
   greedy_decode(model, src, src_mask, max_len, start_symbol)
+  greedy_decode(..., return_scores=True) -> (ys, Scores)   ~ the campaign's torch.topk(prob, 2)
 """
 from .weights import (BOS, DEFAULT_SEED, EOS, PAD, UNK, ModelConfig, load_checkpoint,
                       positional_table, synthetic_state_dict, tensor_order)
@@ -12,7 +13,7 @@ from .weights import (BOS, DEFAULT_SEED, EOS, PAD, UNK, ModelConfig, load_checkp
 __all__ = ["BOS", "EOS", "PAD", "UNK", "DEFAULT_SEED", "ModelConfig", "load_checkpoint",
            "positional_table", "synthetic_state_dict", "tensor_order", "QtxModel",
            "InferenceSession", "run_module", "set_default_model", "greedy_decode",
-           "make_src_mask", "lib"]
+           "greedy_decode_fault", "Scores", "FaultStepRecord", "make_src_mask", "lib"]
 
 
 def __getattr__(name):
@@ -23,7 +24,8 @@ def __getattr__(name):
     if name in ("InferenceSession", "run_module", "set_default_model"):
         from . import session
         return getattr(session, name)
-    if name in ("greedy_decode", "make_src_mask"):
+    if name in ("greedy_decode", "greedy_decode_fault", "Scores", "FaultStepRecord",
+                "make_src_mask"):
         from . import decode
         return getattr(decode, name)
     if name == "lib":

@@ -8,35 +8,80 @@ batched form batch_output.py:659-673): ``ys`` starts with ``start_symbol`` and g
 """
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 
 from .model import QtxModel, to_u8_mask
 from .weights import PAD
 
 
-def greedy_decode(model: QtxModel, src, src_mask, max_len: int, start_symbol: int = 0):
-    """src int64 [B,S] (numpy or torch), src_mask [B,1,S] bool -> ys int64 [B,max_len]."""
+@dataclasses.dataclass
+class FaultStepRecord:
+    """What the reference's campaign prints at the step it corrupts
+    (parallelized_inject_onnx_transformer.py:711-740): torch.topk(prob, 2, dim=1) of the
+    generator on the golden decoder output (its ``out_2``: the same prefix, no fault) and on
+    the faulty one, and whether the chosen token changed.  Arrays [B, 2] / [B]."""
+    step: int
+    golden_ids: object
+    golden_logp: object
+    faulty_ids: object
+    faulty_logp: object
+
+    @property
+    def token_changed(self):
+        return self.golden_ids[..., 0] != self.faulty_ids[..., 0]
+
+
+@dataclasses.dataclass
+class Scores:
+    """The two best tokens of every decode step and their log-probabilities: ``top_ids`` int64
+    and ``top_logp`` float32 [B, max_len-1, 2] (numpy or torch, like the ids they come with);
+    entry t describes the choice of ys[:, t+1], top_ids[..., 0] == ys[:, 1:] (include/qtx.h,
+    scored decode).  ``fault_step``: a decoder-fault decode's FaultStepRecord, else None."""
+    top_ids: object
+    top_logp: object
+    fault_step: FaultStepRecord | None = None
+
+    @property
+    def margin(self):
+        """logp(winner) - logp(runner-up) per step, [B, max_len-1] (>= 0; NaN for a non-finite row)."""
+        return self.top_logp[..., 0] - self.top_logp[..., 1]
+
+
+def greedy_decode(model: QtxModel, src, src_mask, max_len: int, start_symbol: int = 0,
+                  return_scores: bool = False):
+    """src int64 [B,S] (numpy or torch), src_mask [B,1,S] bool -> ys int64 [B,max_len].
+    return_scores=True: (ys, Scores) from the scored KV-cached decode."""
     import torch
     was_numpy = isinstance(src, np.ndarray)
     src_t = torch.from_numpy(np.ascontiguousarray(src)) if was_numpy else src
     B, S = src_t.shape
     srcd = src_t.to(model.device, torch.int64).contiguous()
     md = to_u8_mask(src_mask, model.device).reshape(B, S)
-    ys = model.greedy(srcd, md, max_len=max_len, start=start_symbol)
+    out = model.greedy(srcd, md, max_len=max_len, start=start_symbol, scores=return_scores)
     model.check()
-    if was_numpy:
-        return ys.cpu().numpy()
-    return ys.to(src_t.device)
+    to_host = (lambda t: t.cpu().numpy()) if was_numpy else (lambda t: t.to(src_t.device))
+    if return_scores:
+        ys, top_ids, top_logp = out
+        return to_host(ys), Scores(to_host(top_ids), to_host(top_logp))
+    return to_host(out)
 
 
 def greedy_decode_fault(model: QtxModel, src, src_mask, max_len: int, start_symbol: int = 0,
-                        fault=None, target_inference_number: int = 1):
+                        fault=None, target_inference_number: int = 1,
+                        return_scores: bool = False):
     """Greedy decode with one injected fault, the reference campaign's loop
     (parallelized_inject_onnx_transformer.py:536-720): an encoder fault corrupts the single
     encoder run (memory); a decoder fault corrupts only the decoder run of step
     ``target_inference_number - 1`` — every step recomputes the whole prefix, as the
     reference does, so the faulty step changes that step's token and nothing else directly.
-    src / src_mask as greedy_decode; returns ys int64 [B, max_len] (numpy)."""
+    src / src_mask as greedy_decode; returns ys int64 [B, max_len] (numpy).
+    return_scores=True: (ys, Scores), numpy.  Encoder fault (or none): the scored KV-cached
+    decode.  Decoder fault: every step's top 2 of the faulty decode, and in
+    ``Scores.fault_step`` the campaign's record of the corrupted step (:711-740): the top 2
+    of one extra fault-free decoder run on the same prefix (the reference's ``out_2``) and of
+    the faulty run, and token_changed per sentence."""
     import torch
     src = np.ascontiguousarray(np.asarray(src), np.int64)
     B, S = src.shape
@@ -46,21 +91,39 @@ def greedy_decode_fault(model: QtxModel, src, src_mask, max_len: int, start_symb
     enc_fault = fault if fault is not None and fault.module == 0 else None
     dec_fault = fault if fault is not None and fault.module == 1 else None
     if dec_fault is None:                       # KV-cached fused decode, faulty encoder
-        ys = model.greedy(srcd, md, max_len=max_len, start=start_symbol, fault=enc_fault)
+        out = model.greedy(srcd, md, max_len=max_len, start=start_symbol, fault=enc_fault,
+                           scores=return_scores)
         model.check()
-        return ys.cpu().numpy()
+        if return_scores:
+            return out[0].cpu().numpy(), Scores(out[1].cpu().numpy(), out[2].cpu().numpy())
+        return out.cpu().numpy()
     memory = model.encode(model.embed(srcd, "src"), md)
     model.check()                               # the encode's device errors, before the loop
     ys = torch.full((B, 1), int(start_symbol), dtype=torch.int64, device=dev)
+    tops, record = [], None
     for i in range(max_len - 1):
         T = ys.shape[1]
         tm = torch.tril(torch.ones((T, T), dtype=torch.uint8, device=dev))
-        out = model.decode(model.embed(ys, "tgt"), memory, md, tm,
-                           fault=dec_fault if i == target_inference_number - 1 else None)
-        _, nxt = model.generator(out[:, -1].contiguous(), want_logp=False)
+        faulty = i == target_inference_number - 1
+        y = model.embed(ys, "tgt")
+        out = model.decode(y, memory, md, tm, fault=dec_fault if faulty else None)
+        if not return_scores:
+            _, nxt = model.generator(out[:, -1].contiguous(), want_logp=False)
+        else:
+            top = model.generator_top2(out[:, -1].contiguous())
+            tops.append(top)
+            nxt = top[0][:, 0]
+            if faulty:                          # the golden run of this step (out_2)
+                gold = model.generator_top2(model.decode(y, memory, md, tm)[:, -1].contiguous())
+                record = FaultStepRecord(i, gold[0].cpu().numpy(), gold[1].cpu().numpy(),
+                                         top[0].cpu().numpy(), top[1].cpu().numpy())
         ys = torch.cat([ys, nxt[:, None]], dim=1)
     model.check()
-    return ys.cpu().numpy()
+    if not return_scores:
+        return ys.cpu().numpy()
+    top_ids = torch.stack([t[0] for t in tops], dim=1) if tops else torch.empty((B, 0, 2), dtype=torch.int64)
+    top_logp = torch.stack([t[1] for t in tops], dim=1) if tops else torch.empty((B, 0, 2))
+    return ys.cpu().numpy(), Scores(top_ids.cpu().numpy(), top_logp.cpu().numpy(), record)
 
 
 def make_src_mask(src, pad: int = PAD):

@@ -148,13 +148,26 @@ class QtxModel:
         return out
 
     @_on_device
-    def greedy(self, src, src_mask_u8, max_len: int = 72, start: int = 0, out=None, fault=None):
+    def greedy(self, src, src_mask_u8, max_len: int = 72, start: int = 0, out=None, fault=None,
+               scores: bool = False):
         """src int64 [B,S], src_mask [B,S] u8 -> ids int64 [B,max_len] (device).
-        fault: an optional encoder qtx.fault.Fault."""
+        fault: an optional encoder qtx.fault.Fault.
+        scores=True: (ids, top_ids int64 [B,max_len-1,2], top_logp f32 [B,max_len-1,2]), the
+        two best tokens of every step and their log-probabilities (qtx_greedy_decode_scored)."""
         torch = _torch()
         B, S = src.shape
         ids = out if out is not None else torch.empty((B, max_len), dtype=torch.int64,
                                                       device=self.device)
+        if scores:
+            top_ids = torch.empty((B, max_len - 1, 2), dtype=torch.int64, device=self.device)
+            top_logp = torch.empty((B, max_len - 1, 2), dtype=torch.float32, device=self.device)
+            nb = _lib.lib().qtx_greedy_scored_workspace_size(self.handle, B, S, max_len)
+            ws = self.workspace(nb)
+            _lib.call("qtx_greedy_decode_scored", self.handle, _ptr(src), _ptr(src_mask_u8), B, S,
+                      max_len, int(start), _ptr(ids), _ptr(top_ids), _ptr(top_logp), _ptr(ws),
+                      ws.numel(), C.byref(fault.to_c()) if fault is not None else None,
+                      _stream(self.device))
+            return ids, top_ids, top_logp
         nb = _lib.lib().qtx_greedy_workspace_size(self.handle, B, S, max_len)
         ws = self.workspace(nb)
         if fault is None:
@@ -189,6 +202,20 @@ class QtxModel:
         if return_logits:
             return logp, ids, ws.view(M, V)
         return logp, ids
+
+    @_on_device
+    def generator_top2(self, x):
+        """x [M,512] -> (top_ids int64 [M,2], top_logp f32 [M,2]): torch.topk(prob, 2, dim=1)
+        of the generator's log-probabilities (qtx_generator_top2; no [M,V] log-prob write)."""
+        torch = _torch()
+        M = x.shape[0]
+        V = self.cfg.tgt_vocab
+        top_ids = torch.empty((M, 2), dtype=torch.int64, device=self.device)
+        top_logp = torch.empty((M, 2), dtype=torch.float32, device=self.device)
+        ws = torch.empty((M * V,), dtype=torch.float32, device=self.device)
+        _lib.call("qtx_generator_top2", self.handle, _ptr(x), M, _ptr(top_ids), _ptr(top_logp),
+                  _ptr(ws), ws.numel() * 4, _stream(self.device))
+        return top_ids, top_logp
 
 
 def to_u8_mask(mask, device):
