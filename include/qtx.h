@@ -65,7 +65,12 @@ typedef enum {
 typedef struct qtx_model qtx_model;
 
 /* make_model hyper-parameters (model.py:15-16).  d_model must be 512, d_ff a multiple of
- * 256 up to 2048, n_heads * 64 == d_model.  weight_bits: 8 (W8A8) or 4 (packed int4). */
+ * 256 up to 2048, n_heads * 64 == d_model.  weight_bits: 8 (W8A8) or 4 (packed int4).
+ * Every config qtx_model_create accepts runs every model-level call (tests/
+ * test_gpu_model_configs.py; the kernel chain per config: DESIGN.md, supported shapes):
+ * the row-GEMM encoder / decoder chain needs d_ff % 512 == 0, the fused decode step
+ * d_ff 512 or 2048 and tgt_vocab <= 8192; any other config takes the generic chain and the
+ * unfused step, with the same results. */
 typedef struct {
   int32_t src_vocab, tgt_vocab, n_layers, d_model, d_ff, n_heads, max_len, weight_bits;
 } qtx_config;
@@ -159,7 +164,7 @@ int32_t qtx_model_check(const qtx_model* m, void* stream);
  *   PV  INPUT*:  P*127 int  row = b*Sq + i, col = h*Sk + j   (INPUT16 window: head dims)
  *       WEIGHT*: v element  row = b*Sk + j, col = h*64 + d   (WEIGHT16 window: query rows)
  *       OUTPUT:  context    row = b*Sq + i, col = h*64 + d
- * Requires 8-bit weights. */
+ * Requires 8-bit weights (QTX_E_UNSUPPORTED otherwise); any d_ff. */
 typedef enum {
   QTX_FAULT_NONE = 0, QTX_FAULT_INPUT = 1, QTX_FAULT_WEIGHT = 2, QTX_FAULT_INPUT16 = 3,
   QTX_FAULT_WEIGHT16 = 4, QTX_FAULT_OUTPUT = 5
@@ -228,7 +233,9 @@ int32_t qtx_greedy_decode_fault(const qtx_model* m, const int64_t* src,
  * ids[:, 1:].  fault: NULL or an encoder fault.  Same path selection as the plain decode
  * (fused step with graphs, eager, sub-batches, graphs of several steps, unfused step; the
  * scored step has its own captured graphs).  The fused step's tail (csrc/qtx_decode.hip
- * k_top2_embed) needs tgt_vocab <= 8192 and B * tgt_vocab < 2^30, as the plain one.
+ * k_top2_embed) takes tgt_vocab <= 8192, as the plain one: a model with a larger vocabulary
+ * decodes, plain and scored, with the unfused step, whose tail has no cap (the per-op
+ * qtx_decode_argmax_embed / qtx_decode_top2_embed keep the cap).  B * tgt_vocab < 2^30.
  * Writes exactly ids [B, max_len], top_ids and top_logp [B, max_len-1, 2].
  * ws: qtx_greedy_scored_workspace_size bytes (qtx_greedy_workspace_size is unchanged).
  * QTX_E_UNSUPPORTED with the diagnostic QTX_DBG_TAIL switch. */
@@ -258,7 +265,8 @@ int32_t qtx_generator_top2(const qtx_model* m, const float* x, int32_t M, int64_
 
 /* ---- per-op entry points (parity tests, fault-injection hooks later) ---- */
 
-/* q[r,:] = rint(x[r,:] / s[r]), s[r] = max(max|x[r,:]|, 1e-5) / qmax.  D in {256,512,1024,2048}. */
+/* q[r,:] = rint(x[r,:] / s[r]), s[r] = max(max|x[r,:]|, 1e-5) / qmax.  D a multiple of 256 up to 2048
+ * (this and qtx_layernorm_quant: QTX_E_UNSUPPORTED otherwise). */
 int32_t qtx_row_quant(const float* x, int32_t rows, int32_t D, float qmax, int8_t* q,
                       float* s, void* stream);
 

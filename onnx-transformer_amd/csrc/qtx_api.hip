@@ -392,7 +392,10 @@ int32_t qtx_model_create(const qtx_config* cfg, const float* const* t, int32_t n
     m->enc.resize(NL);
     m->dec.resize(NL);
     for (auto& e : m->enc) { lin(e.qkv, 3 * D, D); lin(e.o, D, D); lin(e.w1, F, D); lin(e.w2, D, F); }
-    for (auto& e : m->enc)
+    // the row GEMM's KP copies and the weight-stationary ones serve the row-GEMM chain only
+    // (row_path: d_ff % 512 == 0; launch_pack_w_kp takes whole 512-column tiles)
+    if (c.d_ff % 512 == 0)
+      for (auto& e : m->enc)
         for (QLin* L : {&e.qkv, &e.o, &e.w1, &e.w2}) L->qkp = ar.take<int8_t>((size_t)L->N * L->K);
     if (c.d_ff % 512 == 0)   // weight-stationary copies (K = 512 GEMMs)
       for (auto& e : m->enc) {
@@ -430,7 +433,8 @@ int32_t qtx_model_create(const qtx_config* cfg, const float* const* t, int32_t n
     float* pe_d = ar.take<float>((size_t)c.max_len * D);
     float* gw = ar.take<float>((size_t)c.tgt_vocab * D);
     float* gb = ar.take<float>(c.tgt_vocab);
-    int8_t* tmp = ar.take<int8_t>((size_t)F * D);
+    // int4 staging of quantize_into: the largest N * K it is called with (D x D where F < D)
+    int8_t* tmp = ar.take<int8_t>((size_t)std::max(F, D) * D);
     m->gen_wt = ar.take<float>((size_t)((c.tgt_vocab + 15) / 16) * 16 * D);
     m->status = ar.take<unsigned>(4 * kStatusSlots);
     return std::make_tuple(norms, src_lut, tgt_lut, pe_d, gw, gb, tmp);
@@ -640,7 +644,7 @@ namespace {
 // scratch for one stack pass over M rows (fp32 residual stream + quant buffers)
 struct Scratch {
   float* x;      // [M, D] residual stream
-  int8_t* a8;    // [M, F] activation ints (max K)
+  int8_t* a8;    // [M, max(D, F)] activation ints (max K)
   float* sa;     // [M]
   float* y;      // [M, max(3D, F)] GEMM output
   int8_t* q8;    // [M, D]   q8, k8, v8 contiguous ([3][M][D]) with sq, sk, sv ([3][M]):
@@ -661,7 +665,9 @@ Scratch carve_scratch(Arena& ar, const qtx_config& c, long M) {
   const int Y = 3 * D > F ? 3 * D : F;
   Scratch s;
   s.x = ar.take<float>(M * D);
-  s.a8 = ar.take<int8_t>((M + 1) * F);    // + 1 row: KP row pairs of an odd M
+  // the inputs of every linear, K = D or F wide (d_ff 256: D is the wider);
+  // + 1 row: KP row pairs of an odd M
+  s.a8 = ar.take<int8_t>((M + 1) * (D > F ? D : F));
   s.sa = ar.take<float>(M);
   s.y = ar.take<float>(M * Y);
   s.q8 = ar.take<int8_t>(3 * M * D); s.k8 = s.q8 + M * D; s.v8 = s.k8 + M * D;
@@ -707,8 +713,10 @@ int quant(const float* x, long ldx, int rows, int D, int8_t* q, float* s, hipStr
 }
 
 int linear(const qtx_config& c, const QLin& L, const int8_t* a8, const float* sa, int M,
-           int flags, const float* res, float* out, long ldo, hipStream_t st) {
+           int flags, const float* res, float* out, long ldo, hipStream_t st,
+           const FaultArgs& fa = FaultArgs{}) {
   GemmArgs g{};
+  g.fault = fa;
   g.A = a8; g.lda = L.K; g.sa = sa;
   const int wb = L.q8 ? 8 : c.weight_bits;
   g.W = L.w8(); g.ldw = wb == 8 ? L.K : L.K / 2; g.sw = L.s; g.bias = L.b;
@@ -836,12 +844,16 @@ AttnArgs attn_args(const Scratch& s, int B, int Sq, int Sk, long kbs_rows) {
 
 // Self-attention sublayer: x += O(attn(LN(x)))   (sublayer_connection.py:15-17,
 // attention.py:39-67).  Q/K/V come out of ONE N=3D GEMM and are quantized per token.
+// fqkv / fo / af: a fault of a fault-injection run in the Q/K/V GEMM, the O projection or
+// the attention MatMuls (fault_for, attn_fault_for), as on the row-GEMM chain.
 int self_attn_block(const qtx_config& c, const QLin& qkv, const QLin& o,
                     const float* const* ln, Scratch& s, int B, int S, const uint8_t* mask,
-                    long m_bs, long m_is, bool dec, hipStream_t st) {
+                    long m_bs, long m_is, bool dec, hipStream_t st,
+                    const FaultArgs& fqkv = FaultArgs{}, const FaultArgs& fo = FaultArgs{},
+                    const AttnFault* af = nullptr) {
   const int D = c.d_model, M = B * S;
   RC(ln_quant(s.x, M, ln, D, s.a8, s.sa, st));
-  RC(linear(c, qkv, s.a8, s.sa, M, 0, nullptr, s.y, 3 * D, st));
+  RC(linear(c, qkv, s.a8, s.sa, M, 0, nullptr, s.y, 3 * D, st, fqkv));
   RC(quant(s.y, 3 * D, M, D, s.q8, s.sq, st));
   RC(quant(s.y + D, 3 * D, M, D, s.k8, s.sk, st));
   RC(quant(s.y + 2 * D, 3 * D, M, D, s.v8, s.sv, st));
@@ -849,19 +861,21 @@ int self_attn_block(const qtx_config& c, const QLin& qkv, const QLin& o,
   a.mask = mask; a.m_bs = m_bs; a.m_is = m_is;
   a.dec = dec;
   HIPCHK(launch_attention(a, st));
+  if (af) HIPCHK(launch_attn_fault_rows(a, *af, st));   // the faulty rows recomputed
   RC(quant(s.ctx, D, M, D, s.a8, s.sa, st));
-  RC(linear(c, o, s.a8, s.sa, M, EPI_RESIDUAL, s.x, s.x, D, st));
+  RC(linear(c, o, s.a8, s.sa, M, EPI_RESIDUAL, s.x, s.x, D, st, fo));
   return QTX_OK;
 }
 
 // FFN sublayer: x += w_2(relu(w_1(LN(x))))   (position_feed_forward.py:11-12)
 int ffn_block(const qtx_config& c, const QLin& w1, const QLin& w2, const float* const* ln,
-              Scratch& s, int M, hipStream_t st) {
+              Scratch& s, int M, hipStream_t st, const FaultArgs& f1 = FaultArgs{},
+              const FaultArgs& f2 = FaultArgs{}) {
   const int D = c.d_model, F = c.d_ff;
   RC(ln_quant(s.x, M, ln, D, s.a8, s.sa, st));
-  RC(linear(c, w1, s.a8, s.sa, M, EPI_RELU, nullptr, s.y, F, st));
+  RC(linear(c, w1, s.a8, s.sa, M, EPI_RELU, nullptr, s.y, F, st, f1));
   RC(quant(s.y, F, M, F, s.a8, s.sa, st));
-  RC(linear(c, w2, s.a8, s.sa, M, EPI_RESIDUAL, s.x, s.x, D, st));
+  RC(linear(c, w2, s.a8, s.sa, M, EPI_RESIDUAL, s.x, s.x, D, st, f2));
   return QTX_OK;
 }
 
@@ -960,7 +974,7 @@ int check_fault(const qtx_model* m, const qtx_fault* f, int module, long B, long
   if (!f || f->kind == QTX_FAULT_NONE) return QTX_OK;
   const qtx_config& c = m->cfg;
   const long M = B * Sq, Ms = B * Ss;
-  if (!row_path(c) || c.weight_bits != 8)
+  if (c.weight_bits != 8)
     return fail(QTX_E_UNSUPPORTED, "fault injection needs 8-bit weights");
   if (f->kind < 0 || f->kind > QTX_FAULT_OUTPUT) return fail(QTX_E_INVALID, "fault kind %d", f->kind);
   if (f->module != module) return fail(QTX_E_INVALID, "fault module %d", f->module);
@@ -1024,9 +1038,14 @@ int encoder_run(const qtx_model* m, const float* x, const uint8_t* mask, int B, 
   const int D = c.d_model, M = B * S;
   if (x != s.x) HIPCHK(hipMemcpyAsync(s.x, x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
   if (!row_path(c)) {
-    for (const EncLayer& L : m->enc) {
-      RC(self_attn_block(c, L.qkv, L.o, L.ln[0], s, B, S, mask, S, 0, false, st));
-      RC(ffn_block(c, L.w1, L.w2, L.ln[1], s, M, st));
+    for (int l = 0; l < c.n_layers; ++l) {
+      const EncLayer& L = m->enc[l];
+      auto fa = [&](GemmId gid) { return fault_for(f, 0, l, gid, M, c); };
+      AttnFault af;
+      const bool attn_f = attn_fault_for(f, 0, l, false, S, S, af);
+      RC(self_attn_block(c, L.qkv, L.o, L.ln[0], s, B, S, mask, S, 0, false, st, fa(G_QKV),
+                         fa(G_O), attn_f ? &af : nullptr));
+      RC(ffn_block(c, L.w1, L.w2, L.ln[1], s, M, st, fa(G_FFN1), fa(G_FFN2)));
     }
     RC(ln_out(s.x, M, m->enc_norm, D, out, st));
     return QTX_OK;
@@ -1165,7 +1184,8 @@ int cross_kv(const qtx_model* m, const float* memory, int Ms, CrossKV& x, hipStr
                    fault_for(f, 1, l, G_CKV, Ms, c)));
       continue;
     }
-    RC(linear(c, m->dec[l].ckv, x.am8, x.sam, Ms, 0, nullptr, x.y, 2 * D, st));
+    RC(linear(c, m->dec[l].ckv, x.am8, x.sam, Ms, 0, nullptr, x.y, 2 * D, st,
+              fault_for(f, 1, l, G_CKV, Ms, c)));
     RC(quant(x.y, 2 * D, Ms, D, x.k8[l], x.sk[l], st));
     RC(quant(x.y + D, 2 * D, Ms, D, x.v8[l], x.sv[l], st));
   }
@@ -1175,19 +1195,21 @@ int cross_kv(const qtx_model* m, const float* memory, int Ms, CrossKV& x, hipStr
 // Cross-attention sublayer: x += O(attn(LN(x) -> Q, memory -> K/V)), decoder.py:32
 int cross_attn_block(const qtx_model* m, const DecLayer& L, int l, Scratch& s,
                      const CrossKV& x, int B, int T, int S, const uint8_t* src_mask,
-                     hipStream_t st) {
+                     hipStream_t st, const FaultArgs& fcq = FaultArgs{},
+                     const FaultArgs& fco = FaultArgs{}, const AttnFault* af = nullptr) {
   const qtx_config& c = m->cfg;
   const int D = c.d_model, M = B * T;
   RC(ln_quant(s.x, M, L.ln[1], D, s.a8, s.sa, st));
-  RC(linear(c, L.cq, s.a8, s.sa, M, 0, nullptr, s.y, D, st));
+  RC(linear(c, L.cq, s.a8, s.sa, M, 0, nullptr, s.y, D, st, fcq));
   RC(quant(s.y, D, M, D, s.q8, s.sq, st));
   AttnArgs a = attn_args(s, B, T, S, S);
   a.k = x.k8[l]; a.sk = x.sk[l]; a.v = x.v8[l]; a.sv = x.sv[l];
   a.mask = src_mask; a.m_bs = S; a.m_is = 0;
   a.dec = 1;
   HIPCHK(launch_attention(a, st));
+  if (af) HIPCHK(launch_attn_fault_rows(a, *af, st));
   RC(quant(s.ctx, D, M, D, s.a8, s.sa, st));
-  RC(linear(c, L.co, s.a8, s.sa, M, EPI_RESIDUAL, s.x, s.x, D, st));
+  RC(linear(c, L.co, s.a8, s.sa, M, EPI_RESIDUAL, s.x, s.x, D, st, fco));
   return QTX_OK;
 }
 
@@ -1306,6 +1328,14 @@ GreedyWS group_view(const GreedyWS& g, const qtx_config& c, int i, int b0, int S
 
 
 // ---- fused decode step (M = B rows, keys <= 128) ----------------------------------------
+// Its kernels exist for the flagship shapes only: the skinny GEMM takes K = 512 or 2048
+// (FFN2: K = d_ff; launch_skinny) and the argmax / top-2 tails a vocabulary of at most
+// ARG_MAXV.  Every other config qtx_model_create accepts decodes with the unfused step,
+// whose kernels have no such limit (greedy_run decides before anything is captured).
+bool fused_step_ok(const qtx_config& c) {
+  return (c.d_ff == 512 || c.d_ff == 2048) && c.tgt_vocab <= ARG_MAXV;
+}
+
 SkinnyArgs skinny(int wbits, const QLin& L, int M, int amode, int flags, float* out, long ldo) {
   SkinnyArgs s{};
   // wbits 8 on a 4-bit model: its unpacked int8 copy
@@ -1592,9 +1622,15 @@ int32_t qtx_decoder_forward_fault(const qtx_model* m, const float* y, const floa
   if (!row_path(c)) {
     for (int l = 0; l < c.n_layers; ++l) {
       const DecLayer& L = m->dec[l];
-      RC(self_attn_block(c, L.qkv, L.o, L.ln[0], s, B, T, tgt_mask, tm_bs, T, true, st));
-      RC(cross_attn_block(m, L, l, s, x, B, T, S, src_mask, st));
-      RC(ffn_block(c, L.w1, L.w2, L.ln[2], s, M, st));
+      auto fa = [&](GemmId gid) { return fault_for(f, 1, l, gid, M, c); };
+      AttnFault af;
+      const bool self_f = attn_fault_for(f, 1, l, false, T, T, af);
+      RC(self_attn_block(c, L.qkv, L.o, L.ln[0], s, B, T, tgt_mask, tm_bs, T, true, st,
+                         fa(G_QKV), fa(G_O), self_f ? &af : nullptr));
+      const bool cross_f = attn_fault_for(f, 1, l, true, T, S, af);
+      RC(cross_attn_block(m, L, l, s, x, B, T, S, src_mask, st, fa(G_CQ), fa(G_CO),
+                          cross_f ? &af : nullptr));
+      RC(ffn_block(c, L.w1, L.w2, L.ln[2], s, M, st, fa(G_FFN1), fa(G_FFN2)));
     }
     RC(ln_out(s.x, M, m->dec_norm, D, out, st));
     return QTX_OK;
@@ -1788,7 +1824,7 @@ int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S
   const int D = c.d_model;
   const uint8_t* src_mask = g.mask;
   int64_t* ids = g.ids;
-  const bool fused = S <= 128 && max_len <= 128 && !knobs().unfused;
+  const bool fused = S <= 128 && max_len <= 128 && fused_step_ok(c) && !knobs().unfused;
 
   // encoder: memory = encode(src_embed(src), src_mask); the cross K/V of every layer
   // (captured into a hipGraph with the steps' replay — QTX_PRE_GRAPH in round 3 — it

@@ -1309,7 +1309,8 @@ hipError_t launch_transpose(const float* in, int R, int Cc, float* out, hipStrea
 // and torch.max of it is index 0: that row's token is 0 (oracle log_softmax_argmax).
 // Then the block writes the next decoder input (embedding + PE of the token).
 // =====================================================================================
-constexpr int ARG_T = 1024, ARG_NV = 8, ARG_MAXV = ARG_T * ARG_NV;
+constexpr int ARG_T = 1024, ARG_NV = 8;
+static_assert(ARG_MAXV == ARG_T * ARG_NV, "the row of logits in the workgroup's registers");
 constexpr float ARG_DELTA = 4.0e-6f;   // >= 2 ulp(16): covers every V <= ARG_MAXV
 
 __device__ __forceinline__ int wave_sum_i32(int v) {

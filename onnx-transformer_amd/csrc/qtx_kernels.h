@@ -11,6 +11,18 @@ enum : int {
   EPI_RESIDUAL = 2,  // out = res + y  (res may alias out)     (sublayer_connection.py:17)
 };
 
+// Fault injected into one GEMM launch (the row GEMM, or k_gemm on the model's fallback chain;
+// the reference's fault models, qtx.h qtx_fault), in GEMM-local coordinates:
+//   FK_INPUT   A[row, col] bit-flipped: acc[row, n] += (flip(a) - a) * W[n, col], n in [lo, hi)
+//   FK_WEIGHT  W[row, col] bit-flipped: acc[m, row] += A[m, col] * (flip(w) - w), m in [lo, hi)
+//   FK_OUTPUT  the MatMul output (before bias) at (row, col) replaced by value
+enum { FK_NONE = 0, FK_INPUT = 1, FK_WEIGHT = 2, FK_OUTPUT = 3 };
+struct FaultArgs {
+  int kind, bit;
+  long row, col, lo, hi;
+  float value;
+};
+
 // C[m, n] = A[m, :] . W[n, :]   (int8 x int8 -> int32, exact)
 // y = ((float(acc) * sa[m]) * sw[n]) + bias[n]  then the EPI_* flags.
 struct GemmArgs {
@@ -23,6 +35,7 @@ struct GemmArgs {
   const float* res; long ldr;     // residual (EPI_RESIDUAL)
   int M, N, K;
   int flags;
+  FaultArgs fault;                // kind FK_NONE: none; 8-bit W only (launch_gemm)
 };
 
 // Skinny (decode) GEMM: M <= 64 rows per workgroup, 16 output columns per workgroup,
@@ -131,18 +144,6 @@ hipError_t launch_attn_trace(const AttnArgs& a, float* qk, float* pc, hipStream_
 //   RE_PARTIAL          (internal: split-K RE_RES_LN at small M) the raw int32 accumulators
 //                       of K range blockIdx.y -> part + blockIdx.y * M * 512 [M,512]
 enum RowEpi { RE_QUANT = 0, RE_RES_LN = 1, RE_RELU_PMAX = 2, RE_RELU_QUANT_PMAX = 3, RE_PARTIAL = 4 };
-// Fault injected into one row-GEMM launch (the reference's fault models, qtx.h qtx_fault),
-// in GEMM-local coordinates:
-//   FK_INPUT   A[row, col] bit-flipped: acc[row, n] += (flip(a) - a) * W[n, col], n in [lo, hi)
-//   FK_WEIGHT  W[row, col] bit-flipped: acc[m, row] += A[m, col] * (flip(w) - w), m in [lo, hi)
-//   FK_OUTPUT  the MatMul output (before bias) at (row, col) replaced by value
-enum { FK_NONE = 0, FK_INPUT = 1, FK_WEIGHT = 2, FK_OUTPUT = 3 };
-struct FaultArgs {
-  int kind, bit;
-  long row, col, lo, hi;
-  float value;
-};
-
 struct RowGemmArgs {
   const int8_t* A; long lda; const float* sa;
   const int8_t* W; long ldw; const float* sw; const float* bias;
@@ -232,6 +233,9 @@ hipError_t launch_pack_gen(const float* W, int V, float* out, hipStream_t st);
 // log_softmax + argmax + next-token embedding + step increment (decode tail):
 //   ids[m, *step + 1] = argmax;  xnext[m] = lut[id]*sqrt(512) + pe[*step + 1];
 //   the last workgroup to finish advances *step (arrive is its private counter).
+// V <= ARG_MAXV (this and launch_top2_embed: hipErrorInvalidValue above it; a model with a
+// larger vocabulary decodes with launch_logsoftmax_argmax / _top2, which have no cap).
+constexpr int ARG_MAXV = 8192;
 hipError_t launch_argmax_embed(const float* logits, int M, int V, int64_t* ids, long ids_bs,
                                int* step, unsigned* arrive, const float* lut, const float* pe,
                                int max_pos, float* xnext, hipStream_t st, int host_s1 = 0);

@@ -121,7 +121,11 @@ hipError_t launch_rows(const RowArgs& a, hipStream_t st) {
   switch (a.D) {
     case 256: k_rows<1><<<grid, block, 0, st>>>(a); break;
     case 512: k_rows<2><<<grid, block, 0, st>>>(a); break;
+    case 768: k_rows<3><<<grid, block, 0, st>>>(a); break;    // every d_ff qtx_model_create takes
     case 1024: k_rows<4><<<grid, block, 0, st>>>(a); break;
+    case 1280: k_rows<5><<<grid, block, 0, st>>>(a); break;
+    case 1536: k_rows<6><<<grid, block, 0, st>>>(a); break;
+    case 1792: k_rows<7><<<grid, block, 0, st>>>(a); break;
     case 2048: k_rows<8><<<grid, block, 0, st>>>(a); break;
     default: return hipErrorInvalidValue;
   }
@@ -242,6 +246,16 @@ __global__ __launch_bounds__(256) void k_gemm(GemmArgs g) {
 
   // epilogue: C/D layout col = lane & 15, row = (lane >> 4) * 4 + e
   const bool relu = g.flags & EPI_RELU, resid = g.flags & EPI_RESIDUAL;
+  // fault-injection runs on the model's fallback chain (GemmArgs::fault): k_gemm_row's exact
+  // integer correction for one bit-flipped int8 operand, or one output value replaced
+  const FaultArgs& f = g.fault;
+  const bool f_in = WBITS == 8 && f.kind == FK_INPUT, f_w = WBITS == 8 && f.kind == FK_WEIGHT;
+  const bool f_out = WBITS == 8 && f.kind == FK_OUTPUT;
+  int delta = 0;
+  if (f_in || f_w) {
+    const int8_t orig = f_in ? g.A[f.row * g.lda + f.col] : g.W[f.row * g.ldw + f.col];
+    delta = (int)(int8_t)(orig ^ (1 << f.bit)) - (int)orig;
+  }
 #pragma unroll
   for (int j = 0; j < FN; ++j) {
     const int col = bn0 + wn * TN + j * 16 + fr;
@@ -253,7 +267,12 @@ __global__ __launch_bounds__(256) void k_gemm(GemmArgs g) {
       for (int e = 0; e < 4; ++e) {
         const int row = bm0 + wm * TM + i * 16 + fg * 4 + e;
         if (row >= g.M) continue;
+        if (f_in && row == f.row && col >= f.lo && col < f.hi)
+          acc[i][j][e] += delta * (int)g.W[(long)col * g.ldw + f.col];
+        if (f_w && col == f.row && row >= f.lo && row < f.hi)
+          acc[i][j][e] += delta * (int)g.A[(long)row * g.lda + f.col];
         float y = ((float)acc[i][j][e] * g.sa[row]) * swc + bc;
+        if (f_out && row == f.row && col == f.col) y = f.value + bc;
         if (relu) y = y > 0.0f ? y : 0.0f;
         if (resid) y = g.res[(long)row * g.ldr + col] + y;
         g.out[(long)row * g.ldo + col] = y;
@@ -266,7 +285,9 @@ hipError_t launch_gemm(const GemmArgs& g, int wbits, hipStream_t st) {
   if (g.M <= 0 || g.N <= 0) return hipSuccess;
   if (g.K % 64 != 0 || (wbits != 8 && wbits != 4)) return hipErrorInvalidValue;
   const dim3 block(256);
-  if (wbits == 8 && !knobs().gemm128) {       // QTX_GEMM128 (QTX_DIAG build): timing experiments
+  if (g.fault.kind != FK_NONE && wbits != 8) return hipErrorInvalidValue;
+  // (k_gemm256 carries no fault: a fault-injection run takes k_gemm)
+  if (wbits == 8 && !knobs().gemm128 && g.fault.kind == FK_NONE) {   // QTX_GEMM128 (QTX_DIAG build): timing experiments
     const hipError_t e = launch_gemm256(g, st);
     if (e != hipErrorNotSupported) return e;
   }
