@@ -464,6 +464,18 @@ int32_t qtx_decode_top2_embed(const qtx_model* m, const float* logits, int32_t M
                               int64_t ids_bs, int64_t* top_ids, float* top_logp,
                               int32_t* step_dev, float* x_next, void* stream);
 
+/* The decode step's generator launch: logits [M, tgt_vocab] = generator(final LayerNorm(x)),
+ * x fp32 [M, d_model] (decoder.py:16, generator.py:14).  rec (may be NULL): float
+ * [M, ceil(tgt_vocab / 16), 4], one record per row and 16-column strip of the vocabulary, which
+ * the plain decode's next step reduces to the token instead of a tail kernel of its own:
+ * {m1, m2, i1, flags} with m1 = the strip's maximum (fmaxf from -3.0e38f), m2 = the next value
+ * in descending order (m2 == m1 for a duplicate of the maximum; -3.0e38f when there is none),
+ * i1 (int32 bits) = the smallest vocabulary index holding m1 (INT32_MAX: none), flags (int32
+ * bits) bit 0 = a NaN or +inf in the strip, bit 1 = a value above -inf.  The logits do not
+ * depend on rec. */
+int32_t qtx_decode_generator(const qtx_model* m, const float* x, int32_t M, float* logits,
+                             float* rec, void* stream);
+
 /* An empty one-wave kernel on `stream`: the dependent-launch floor that bench.py subtracts
  * from a chain of launches to get per-kernel durations (measurement only, no reference
  * counterpart). */

@@ -1232,6 +1232,7 @@ struct GreedyWS {
   float* memory;
   float* xo;
   float* logits;
+  float* rec;         // [B][ceil(V/16)][4] the generator's per-strip top-2 records (folded tail)
   int* step;          // [0] = decode position, [1] = argmax arrival counter
   float* pmax_a;      // [8][B]    per-head absmax of the attention context (A_F32Q input)
   float* pmax_f;      // [F/16][B] per-column-tile absmax of FFN1's output
@@ -1295,6 +1296,7 @@ GreedyWS carve_greedy(Arena& ar, const qtx_config& c, int B, int S, int max_len,
   g.gsteps = ar.take<int>(4 * QTX_MAX_GROUPS);
   g.ids = ar.take<int64_t>((size_t)B * max_len);
   g.mask = ar.take<uint8_t>((size_t)B * S);
+  g.rec = ar.take<float>((size_t)B * ((c.tgt_vocab + 15) / 16) * 4);
   if (scored) {
     g.top_ids = ar.take<int64_t>((size_t)B * (max_len - 1) * 2);
     g.top_logp = ar.take<float>((size_t)B * (max_len - 1) * 2);
@@ -1316,6 +1318,7 @@ GreedyWS group_view(const GreedyWS& g, const qtx_config& c, int i, int b0, int S
     v.cross.sk[l] += b0 * S; v.cross.sv[l] += b0 * S;
   }
   v.logits += (long)b0 * c.tgt_vocab;
+  v.rec += (long)b0 * ((c.tgt_vocab + 15) / 16) * 4;
   v.pmax_a += (long)8 * b0;               // each sub-batch: its own [P][rows] block
   v.pmax_f += (long)(c.d_ff / 16) * b0;
   v.step = g.gsteps + 4 * i;
@@ -1371,6 +1374,13 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
   // neither read nor advanced) or from the device counter (QTX_DEVICE_STEP, or a step replayed
   // at several positions)
   const bool host_pos = t_host >= 0 && !knobs().device_step;
+  // The tail folded into the next step's first launch (plain decode, int8 kernels, positions
+  // from the host; QTX_NO_TAIL_FOLD: never): the generator also writes per-strip top-2 records,
+  // and from step 1 on layer 0's LN+QKV launch decides the previous step's token from them,
+  // embeds it and stores ids / x itself (launch_skinny_tok) — a step is then 49 launches.
+  // Only the last step still ends with the argmax kernel.
+  const bool fold = !knobs().no_tail_fold && host_pos && !g.top_ids && wb == 8 && fused_ln &&
+                    !knobs().ablate && !knobs().dbg_tail;
   Scratch& s = g.dec;
   // Timing experiments only (wrong results): QTX_ABLATE=<bitmask> drops kernel classes
   // from the step (replaced by an empty kernel with QTX_ABLATE_NOP=1) to measure what
@@ -1413,7 +1423,17 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
   for (int l = 0; l < c.n_layers; ++l) {
     const DecLayer& L = m->dec[l];
     SkinnyArgs a;
-    RC(ln_linear(L.qkv, L.ln[0], 0, s.y, 3 * D, 2));
+    if (fold && l == 0 && t_host >= 1) {
+      SkinnyArgs k = skinny(wb, L.qkv, B, A_LN, 0, s.y, 3 * D);
+      k.ln_a = L.ln[0][0]; k.ln_b = L.ln[0][1];
+      TokArgs tk{};
+      tk.rec = g.rec; tk.logits = g.logits; tk.V = c.tgt_vocab; tk.lut = m->tgt_lut;
+      tk.pe = m->pe; tk.max_pos = c.max_len; tk.pos = t_host; tk.ids = ids; tk.ids_bs = max_len;
+      tk.xres = s.x;
+      HIPCHK(launch_skinny_tok(k, tk, st));
+    } else {
+      RC(ln_linear(L.qkv, L.ln[0], 0, s.y, 3 * D, 2));
+    }
     DecAttnArgs at{};
     at.y = s.y; at.ldy = 3 * D; at.kv_new = 1; at.step = g.step;
     at.kc = g.kc[l]; at.vc = g.vc[l]; at.skc = g.skc[l]; at.svc = g.svc[l]; at.kv_bs = max_len;
@@ -1460,7 +1480,8 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
     return QTX_OK;
   }
   QTX_RUN(256, launch_generator_mfma(s.x, D, B, m->dec_norm[0], m->dec_norm[1], m->gen_wt,
-                                     m->gen_b, c.tgt_vocab, g.logits, st));
+                                     m->gen_b, c.tgt_vocab, g.logits, st, fold ? g.rec : nullptr));
+  if (fold && t_host + 2 < max_len) return QTX_OK;   // the next step's first launch is the tail
   if (g.top_ids)   // scored decode: the tail that also writes the step's two best (id, logp)
     QTX_RUN(256, launch_top2_embed(g.logits, B, c.tgt_vocab, ids, max_len, g.top_ids, g.top_logp,
                                    g.step, reinterpret_cast<unsigned*>(g.step + 1), m->tgt_lut,
@@ -2185,6 +2206,20 @@ int32_t qtx_decode_attention(int32_t kv_new, const float* y, int64_t ldy, int8_t
 
 int32_t qtx_debug_nop(void* stream) {
   HIPCHK(launch_nop((hipStream_t)stream));
+  return QTX_OK;
+}
+
+int32_t qtx_decode_generator(const qtx_model* m, const float* x, int32_t M, float* logits,
+                             float* rec, void* stream) {
+  if (!m || !x || !logits) return fail(QTX_E_INVALID, "null argument");
+  if (M <= 0) return QTX_OK;
+  if (!aligned16(x) || (rec && !aligned16(rec)))
+    return fail(QTX_E_INVALID, "x / rec must be 16-byte aligned");
+  const hipError_t e = launch_generator_mfma(x, m->cfg.d_model, M, m->dec_norm[0], m->dec_norm[1],
+                                             m->gen_wt, m->gen_b, m->cfg.tgt_vocab, logits,
+                                             (hipStream_t)stream, rec);
+  if (e == hipErrorInvalidValue) return fail(QTX_E_UNSUPPORTED, "M * tgt_vocab >= 2^30");
+  HIPCHK(e);
   return QTX_OK;
 }
 

@@ -153,6 +153,24 @@ __device__ __forceinline__ int wave_min_i32(int v) {
   return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
              min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
+// min / bitwise or over each 16-lane DPP row (every lane of the row gets the result)
+template <int CTRL>
+__device__ __forceinline__ int dpp_i32(int v) {
+  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
+}
+__device__ __forceinline__ int row16_min_i32(int v) {
+  v = min(v, dpp_i32<0xB1>(v));
+  v = min(v, dpp_i32<0x4E>(v));
+  v = min(v, dpp_i32<0x141>(v));
+  return min(v, dpp_i32<0x140>(v));
+}
+__device__ __forceinline__ int row16_or_i32(int v) {
+  v |= dpp_i32<0xB1>(v);
+  v |= dpp_i32<0x4E>(v);
+  v |= dpp_i32<0x141>(v);
+  return v | dpp_i32<0x140>(v);
+}
+
 __device__ __forceinline__ int wave_max_i32(int v) {
   auto d = [](int x, auto ctrl) {
     return __builtin_amdgcn_update_dpp(int(0x80000000), x, decltype(ctrl)::value, 0xF, 0xF, false);

@@ -11,6 +11,8 @@
 //                   generator.py:14-15, decoder.py:16
 //   k_argmax_embed  log_softmax + first argmax + next-token embedding + step advance
 //                   onnx_reference_inference.py:632,640-643
+//   k_skinny_wide_tok  the same decision folded into the next step's first launch (layer 0's
+//                   LN+QKV), from the generator's per-strip top-2 records
 //   k_top2_embed    its scored form: the two best (id, logp) of the row as well
 //                   parallelized_inject_onnx_transformer.py:718-740
 //
@@ -1173,11 +1175,15 @@ hipError_t launch_quant_h2048(const float* X, long ldx, int M, int8_t* q, float*
 // =====================================================================================
 constexpr int GEN_Q = 32;   // float4 groups of 4 k-steps per lane (K = 512)
 
-// (parameters in order of first use: all but `logits` arrive preloaded in SGPRs)
+// (parameters in order of first use: all but `logits` / `rec` arrive preloaded in SGPRs)
+// REC: also the per-strip top-2 records (qtx_kernels.h launch_generator_mfma); without it the
+// kernel is what it was before the records existed
+template <bool REC>
 __global__ __launch_bounds__(1024) void k_generator_mfma(const float* Wm, int V, int M,
                                                          const float* bias, const float* x,
                                                          long ldx, const float* ln_a,
-                                                         const float* ln_b, float* logits) {
+                                                         const float* ln_b, float* logits,
+                                                         float* rec) {
   __shared__ __attribute__((aligned(16))) float X[16][514];   // stride 514: conflict-free reads
   __shared__ __attribute__((aligned(16))) v4f part[3][4][64];  // quarters 1..3: [strip][lane]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1192,7 +1198,9 @@ __global__ __launch_bounds__(1024) void k_generator_mfma(const float* Wm, int V,
   const int m0 = rb * 16;
   const int vcol = strip * 16 + fr;
   QTX_STAMP(0);
-  // 1. the quarter strip's B operands, all in flight before anything else
+  // 1. the quarter strip's B operands, all in flight before anything else (the row and the
+  //    LayerNorm parameters first — the order of the skinny GEMMs — gained 0.02 ms per decode
+  //    here, less than the A/B's bar: DESIGN.md §5, round 8)
   constexpr int QQ = GEN_Q / 4;
   const unsigned wo = 16u * (unsigned)((min(strip, nstrip - 1) * GEN_Q + QQ * qq) * 64 + lane);
   float4 wq[QQ];
@@ -1233,24 +1241,68 @@ __global__ __launch_bounds__(1024) void k_generator_mfma(const float* Wm, int V,
   if (qq) part[qq - 1][sw][lane] = acc;
   __syncthreads();
   QTX_STAMP(2);
-  if (qq || vcol >= V) return;
+  if constexpr (!REC) {
+    if (qq || vcol >= V) return;
+    const v4f p1 = part[0][sw][lane], p2 = part[1][sw][lane], p3 = part[2][sw][lane];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int m = m0 + 4 * fg + e;
+      if (m < M) st_at(logits, 4u * (unsigned)(m * V + vcol), ((acc[e] + p1[e]) + (p2[e] + p3[e])) + bv);
+    }
+    QTX_STAMP(3);
+    return;
+  }
+  if (qq) return;
   const v4f p1 = part[0][sw][lane], p2 = part[1][sw][lane], p3 = part[2][sw][lane];
+  const bool vok = vcol < V;
+  float y[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int m = m0 + 4 * fg + e;
-    if (m < M) st_at(logits, 4u * (unsigned)(m * V + vcol), ((acc[e] + p1[e]) + (p2[e] + p3[e])) + bv);
+    y[e] = ((acc[e] + p1[e]) + (p2[e] + p3[e])) + bv;
+    if (vok && m < M) st_at(logits, 4u * (unsigned)(m * V + vcol), y[e]);
   }
   QTX_STAMP(3);
+  // 4. the strip's top-2 record of each row (launch_skinny_tok finishes the reduction): the
+  //    16 columns of row 4 fg + e are the 16 lanes of DPP row fg — no cross-wave step
+  if (strip >= nstrip) return;                            // (wave-uniform)
+  float m1[4], m2[4];
+  int i1[4], fl[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    m1[e] = row16_max(vok ? fmaxf(-3.0e38f, y[e]) : -3.0e38f);
+    fl[e] = vok ? ((y[e] < __builtin_inff() ? 0 : 1) | (y[e] > -__builtin_inff() ? 2 : 0)) : 0;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    i1[e] = row16_min_i32(vok && y[e] == m1[e] ? vcol : 0x7fffffff);
+    fl[e] = row16_or_i32(fl[e]);
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    m2[e] = row16_max(vok && vcol != i1[e] ? fmaxf(-3.0e38f, y[e]) : -3.0e38f);
+  if (fr == 0) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int m = m0 + 4 * fg + e;
+      if (m < M)
+        st_at(reinterpret_cast<float4*>(rec), 16u * (unsigned)(m * nstrip + strip),
+              make_float4(m1[e], m2[e], __int_as_float(i1[e]), __int_as_float(fl[e])));
+    }
+  }
 }
 
 hipError_t launch_generator_mfma(const float* x, long ldx, int M, const float* ln_a,
                                  const float* ln_b, const float* Wm, const float* b, int V,
-                                 float* logits, hipStream_t st) {
+                                 float* logits, hipStream_t st, float* rec) {
   if (M <= 0) return hipSuccess;
   if ((long)M * V >= (1L << 30) || (long)M * ldx >= (1L << 30)) return hipErrorInvalidValue;   // 32-bit offsets
   const int ngroup = (V + 63) / 64, nrb = (M + 15) / 16;
   const unsigned grid = 8u * nrb * ((ngroup + 7) / 8);
-  k_generator_mfma<<<dim3(grid), dim3(1024), 0, st>>>(Wm, V, M, b, x, ldx, ln_a, ln_b, logits);
+  if (rec)
+    k_generator_mfma<true><<<dim3(grid), dim3(1024), 0, st>>>(Wm, V, M, b, x, ldx, ln_a, ln_b, logits, rec);
+  else
+    k_generator_mfma<false><<<dim3(grid), dim3(1024), 0, st>>>(Wm, V, M, b, x, ldx, ln_a, ln_b, logits, rec);
   return hipGetLastError();
 }
 
@@ -1455,6 +1507,205 @@ hipError_t launch_argmax_embed(const float* logits, int M, int V, int64_t* ids, 
   if (V > ARG_MAXV || host_s1 < 0 || (long)M * V >= (1L << 30)) return hipErrorInvalidValue;
   k_argmax_embed<<<dim3(M), dim3(ARG_T), 0, st>>>(logits, V, host_s1, step, pe, lut, max_pos,
                                                   ids_bs, ids, arrive, xnext);
+  return hipGetLastError();
+}
+
+// =====================================================================================
+// k_skinny_wide_tok: the decode tail folded into layer 0's LN+QKV launch (steps after the
+// first of a plain decode whose positions the host knows).  k_skinny_wide<RB, 8, A_LN, 0>
+// with another source of its rows: the wave that owns row m finishes the vocabulary
+// reduction the generator began (k_generator_mfma's per-strip records: <= 8 per lane, merged
+// lane-locally, then over the wave — max / top-2 is order-free), decides the token exactly as
+// k_argmax_embed does, gathers its embedding and forms x = e * sqrt(512) + pe, the row the
+// A_LN prologue would have loaded.  The near-tie path is k_argmax_embed's canonical
+// lane-split sum with one wave holding the whole row (lane l: logits l, l + 64, ... in order).
+// Every column workgroup decides the same token from the same records; those of the first
+// column block store x (the residual of layer 0's O-projection) and the id.  The records'
+// and the PE row's addresses come from preloaded arguments; the weights follow them.
+// =====================================================================================
+struct TkLead {
+  uint64_t rec, pe_row; int M, V; uint64_t W; int ldw, N; uint64_t sw, lut;
+};
+struct TkTail {
+  const float* ln_a; const float* ln_b; const float* bias; const float* logits;
+  float* out; float* xres; int64_t* ids; long ids_bs; int pos, ldo;
+};
+struct TokRec { float m1, m2; int i1, fl; };
+// the record of the union of two disjoint sets: m1 by "larger value, then smaller index", m2
+// the largest of the loser's m1 and both m2, flags or'ed (commutative and associative)
+__device__ __forceinline__ void tok_merge(TokRec& a, float m1, float m2, int i1, int fl) {
+  const bool lead = (m1 > a.m1) | ((m1 == a.m1) & (i1 < a.i1));   // (no branches)
+  const float loser = lead ? a.m1 : m1;
+  a.m2 = fmaxf(fmaxf(a.m2, m2), loser);
+  a.m1 = lead ? m1 : a.m1;
+  a.i1 = lead ? i1 : a.i1;
+  a.fl |= fl;
+}
+template <int CTRL>
+__device__ __forceinline__ void tok_merge_dpp(TokRec& a) {   // (the partner lane's set is disjoint)
+  const float m1 = dpp<CTRL>(a.m1), m2 = dpp<CTRL>(a.m2);
+  const int i1 = dpp_i32<CTRL>(a.i1), fl = dpp_i32<CTRL>(a.fl);
+  tok_merge(a, m1, m2, i1, fl);
+}
+// the first argmax of logp = (x - mx) - lse over one row of logits, one wave
+__device__ __forceinline__ int tok_exact(const float* row, int V, float mx, int lane) {
+  float ls = 0.0f;
+  for (int v = lane; v < V; v += 64) ls = ls + qexp(row[v] - mx);
+  ls = wave_sum(ls);
+  const float lse = logf(ls);
+  float best = -3.0e38f;
+  int bj = 0x7fffffff;
+  for (int v = lane; v < V; v += 64) {
+    const float lp = (row[v] - mx) - lse;
+    if (lp > best) { best = lp; bj = v; }
+  }
+  const float wb = wave_max(best);
+  return wave_min_i32(best == wb ? bj : 0x7fffffff);
+}
+
+template <int RB>
+__global__ __launch_bounds__(256) void k_skinny_wide_tok(QTX_KA_PARAMS, TkTail kt) {
+  const TkLead l = __builtin_bit_cast(TkLead, QTX_KA_VALS);
+  constexpr int K = 512, NS = K / 64, LDA = K + 16, RPW = RB / 4;
+  constexpr int NR = ARG_MAXV / 16 / 64;   // records per lane
+  static_assert(RB == 4 || RB == 8, "one or two rows per wave");
+  __shared__ __attribute__((aligned(16))) uint8_t As[16 * LDA];
+  __shared__ float sas[16];
+  __shared__ v4i tail[4][4 * RB];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int fr = lane & 15, fg = lane >> 4;
+  const int n0 = blockIdx.x * 64 + 16 * wave, m0 = blockIdx.y * RB;
+  const int M = l.M, V = l.V, nstrip = (V + 15) >> 4;
+  // 1. the rows' records (lane: strips lane, lane + 64, ...; clamped, masked below) and the
+  //    PE row of the position
+  float4 rc[RPW][NR], pe[2];
+#pragma unroll
+  for (int j = 0; j < RPW; ++j) {
+    const int m = min(m0 + wave + 4 * j, M - 1);
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+      rc[j][i] = ld_at(ka_ptr<const float4>(l.rec), 16u * (unsigned)(m * nstrip + min(lane + 64 * i, nstrip - 1)));
+  }
+#pragma unroll
+  for (int c = 0; c < 2; ++c) pe[c] = ld_at(ka_ptr<const float4>(l.pe_row), 16u * (unsigned)(lane + 64 * c));
+  // 2. this lane's W fragments (all of K) and the epilogue operands (N % 64 == 0: in range)
+  const int col = n0 + fr;
+  uint4 wf[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+    wf[s] = ld_at(ka_ptr<const uint4>(l.W), (unsigned)(col * l.ldw + 64 * s + 16 * fg));
+  const float swc = ld_at(ka_ptr<const float>(l.sw), 4u * col);
+  __builtin_amdgcn_sched_barrier(0);   // as in k_skinny: trailing arguments from here on
+  const float bc = ld_at(kt.bias, 4u * col);
+  float ga[2][4], gb[2][4];
+  ln_params512(kt.ln_a, kt.ln_b, lane, ga, gb);
+  // 3. the token of each row and its input row x
+  float v[RPW][2][4];
+  int ids[RPW];
+#pragma unroll
+  for (int j = 0; j < RPW; ++j) {
+    const int m = min(m0 + wave + 4 * j, M - 1);
+    TokRec t{-3.0e38f, -3.0e38f, 0x7fffffff, 0};
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      const bool in = lane + 64 * i < nstrip;
+      tok_merge(t, in ? rc[j][i].x : -3.0e38f, in ? rc[j][i].y : -3.0e38f,
+                in ? __float_as_int(rc[j][i].z) : 0x7fffffff, in ? __float_as_int(rc[j][i].w) : 0);
+    }
+    tok_merge_dpp<0xB1>(t);
+    tok_merge_dpp<0x4E>(t);
+    tok_merge_dpp<0x141>(t);
+    tok_merge_dpp<0x140>(t);
+    TokRec w{lane_f(t.m1, 0), lane_f(t.m2, 0), __builtin_amdgcn_readlane(t.i1, 0),
+             __builtin_amdgcn_readlane(t.fl, 0)};
+#pragma unroll
+    for (int q = 16; q < 64; q += 16)
+      tok_merge(w, lane_f(t.m1, q), lane_f(t.m2, q), __builtin_amdgcn_readlane(t.i1, q),
+                __builtin_amdgcn_readlane(t.fl, q));
+    int id;
+    if ((w.fl & 1) || !(w.fl & 2)) {
+      id = 0;                              // torch.max of an all-NaN log_softmax row
+    } else if (!(w.m2 > w.m1 - ARG_DELTA) && w.i1 != 0x7fffffff) {
+      id = w.i1;                           // exactly one value above max - ARG_DELTA
+    } else {                               // near-tie: the exact log-softmax decides
+      id = tok_exact(kt.logits + (long)m * V, V, w.m1, lane);
+    }
+    ids[j] = max(min(id, V - 1), 0);       // keeps the embedding gather in bounds, whatever
+  }
+  // next decoder input: tgt_embed(id) at the position (every load in flight before its use)
+  float4 em[RPW][2];
+#pragma unroll
+  for (int j = 0; j < RPW; ++j)
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+      em[j][c] = ld_at(ka_ptr<const float4>(l.lut), 16u * (unsigned)(ids[j] * 128 + lane + 64 * c));
+#pragma unroll
+  for (int j = 0; j < RPW; ++j) {
+    const int r = wave + 4 * j, m = min(m0 + r, M - 1);
+    const float sc = 0x1.6a09e6p+4f;
+    const bool st = blockIdx.x == 0 && m0 + r < M;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const float4 e = em[j][c];
+      const float4 x = make_float4(e.x * sc + pe[c].x, e.y * sc + pe[c].y, e.z * sc + pe[c].z,
+                                   e.w * sc + pe[c].w);
+      v[j][c][0] = x.x; v[j][c][1] = x.y; v[j][c][2] = x.z; v[j][c][3] = x.w;
+      if (st) st_at(reinterpret_cast<float4*>(kt.xres), 16u * (unsigned)(m * 128 + lane + 64 * c), x);
+    }
+    if (st && lane == 0 && kt.pos < kt.ids_bs) kt.ids[m * kt.ids_bs + kt.pos] = ids[j];
+  }
+  // 4. LayerNorm + per-token quantization into LDS, as the A_LN prologue
+  {
+    uint32_t q[RPW][2];
+    float sc[RPW];
+    ln_rows512<RPW>(v, ga, gb);
+    quant_rows512<RPW>(v, q, sc);
+#pragma unroll
+    for (int j = 0; j < RPW; ++j) {
+      const int r = wave + 4 * j;
+      const bool ok = m0 + r < M;
+      uint32_t* dst = reinterpret_cast<uint32_t*>(As + r * LDA);
+      dst[lane] = ok ? q[j][0] : 0u;
+      dst[lane + 64] = ok ? q[j][1] : 0u;
+      if (lane == 0) sas[r] = ok ? sc[j] : 0.0f;
+    }
+  }
+  __syncthreads();
+  // 5. MFMA over all of K and the epilogue of k_skinny_wide (flags 0)
+  v4i acc = v4i{0, 0, 0, 0};
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const v4i afr = *reinterpret_cast<const v4i*>(As + fr * LDA + 64 * s + 16 * fg);
+    acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(afr, __builtin_bit_cast(v4i, wf[s]), acc, 0, 0, 0);
+  }
+  if (fg < RPW) tail[wave][16 * fg + fr] = acc;
+  __builtin_amdgcn_wave_barrier();      // as in k_skinny_wide
+#pragma unroll
+  for (int j = 0; j < RPW; ++j) {
+    const int vv = reinterpret_cast<const int*>(&tail[wave][16 * j + fr])[fg];
+    const int r = fg + 4 * j, row = m0 + r;
+    const float y = ((float)vv * sas[r]) * swc + bc;
+    if (row < M) st_at(kt.out, 4u * (unsigned)(row * kt.ldo + col), y);
+  }
+}
+
+hipError_t launch_skinny_tok(const SkinnyArgs& g, const TokArgs& t, hipStream_t st) {
+  if (g.M <= 0) return hipSuccess;
+  const long lim = 1L << 30;   // 32-bit byte offsets, as launch_skinny
+  if (g.K != 512 || g.N % 64 || g.flags || g.ldw != 512 || t.V < 1 || t.V > ARG_MAXV ||
+      t.pos < 1 || (long)g.M * t.V >= lim || (long)g.M * g.ldo >= lim || (long)g.N * g.ldw >= lim)
+    return hipErrorInvalidValue;
+  TkLead l{};
+  l.rec = ka_int(t.rec); l.pe_row = ka_int(t.pe + (long)std::min(t.pos, t.max_pos - 1) * 512);
+  l.M = g.M; l.V = t.V; l.W = ka_int(g.W); l.ldw = (int)g.ldw; l.N = g.N;
+  l.sw = ka_int(g.sw); l.lut = ka_int(t.lut);
+  const TkTail kt{g.ln_a, g.ln_b, g.bias, t.logits, g.out, t.xres, t.ids, t.ids_bs, t.pos, (int)g.ldo};
+  const KaLead ka = ka_pack(l);
+  // rows per workgroup as skinny_mode's N-split LayerNorm GEMMs
+  if (g.M >= 96)
+    k_skinny_wide_tok<8><<<dim3(g.N / 64, (g.M + 7) / 8), 256, 0, st>>>(QTX_KA_ARGS(ka), kt);
+  else
+    k_skinny_wide_tok<4><<<dim3(g.N / 64, (g.M + 3) / 4), 256, 0, st>>>(QTX_KA_ARGS(ka), kt);
   return hipGetLastError();
 }
 

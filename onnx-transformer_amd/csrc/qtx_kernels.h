@@ -62,6 +62,22 @@ struct SkinnyArgs {
   int M, N, K, flags;
 };
 
+// The decode tail folded into layer 0's LN+QKV launch (k_skinny_wide_tok): the token of
+// position pos is decided in the prologue from the previous step's generator output — the
+// per-strip top-2 records `rec` [M][ceil(V/16)][4] (launch_generator_mfma) and, for a near-tie,
+// the logits [M][V] themselves — exactly as k_argmax_embed decides it; the row
+// x = lut[id] * sqrt(512) + pe[pos] then goes through the A_LN prologue.  The workgroups of
+// the first column block store x to xres [M][512] and ids[m * ids_bs + pos].
+struct TokArgs {
+  const float* rec; const float* logits; int V;
+  const float* lut; const float* pe; int max_pos;
+  int pos;                     // >= 1: the position decided (the host knows it)
+  int64_t* ids; long ids_bs;
+  float* xres;
+};
+// g: an A_LN SkinnyArgs (K = 512, N % 64 == 0, flags 0; X / ldx unused), 8-bit weights
+hipError_t launch_skinny_tok(const SkinnyArgs& g, const TokArgs& t, hipStream_t st);
+
 // Fused decode attention: one wave per (sentence b, head h), one query.
 //   self  (kv_new != 0): q/k/v rows from y [B, 3*512] fp32 are quantized per token;
 //                        k/v appended to the caches at position *step; keys 0..*step.
@@ -225,9 +241,14 @@ hipError_t launch_quant_h2048(const float* X, long ldx, int M, int8_t* q, float*
                               hipStream_t st);
 // generator with the final LayerNorm fused in (ln_a may be null = no LN)
 // the same on fp32 MFMA (bit-identical chain); Wt = generator weight transposed [512][V]
+// rec (may be null): beside the logits, one 16-byte record {m1, m2, i1, flags} per (row,
+// 16-column strip), [M][ceil(V/16)] — the strip's maximum over its columns < V (fmaxf from
+// -3.0e38f), the next value in descending order (m2 == m1 for a duplicate), the smallest
+// vocabulary index holding m1 (INT_MAX: none), flags bit 0 = a NaN or +inf, bit 1 = a value
+// above -inf (launch_skinny_tok finishes the reduction)
 hipError_t launch_generator_mfma(const float* x, long ldx, int M, const float* ln_a,
                                  const float* ln_b, const float* Wt, const float* b, int V,
-                                 float* logits, hipStream_t st);
+                                 float* logits, hipStream_t st, float* rec = nullptr);
 hipError_t launch_transpose(const float* in, int R, int C, float* out, hipStream_t st);
 hipError_t launch_pack_gen(const float* W, int V, float* out, hipStream_t st);
 // log_softmax + argmax + next-token embedding + step increment (decode tail):

@@ -34,6 +34,9 @@ struct Knobs {
   bool no_graph = false;     // QTX_NO_GRAPH: eager decode launches
   bool ffn_qkernel = false;  // QTX_FFN_QKERNEL: the FFN hidden quantized by its own kernel
                              // (the default from B >= 96; forced below it by tests)
+  bool no_tail_fold = false; // QTX_NO_TAIL_FOLD: every fused step ends with the argmax kernel
+                             // (50 launches) instead of folding it into the next step's
+                             // first launch
   int decode_groups = 0;     // QTX_DECODE_GROUPS: sub-batch graphs (0: by batch size)
   int graph_steps = 0;       // QTX_GRAPH_STEPS: decode steps per graph (0: all)
   long ws_min_m = 2048;      // QTX_WS_MIN_M: weight-stationary from this many rows

@@ -32,6 +32,7 @@ Knobs read_env() {
   k.unfused = flag("QTX_UNFUSED");
   k.no_graph = flag("QTX_NO_GRAPH");
   k.ffn_qkernel = flag("QTX_FFN_QKERNEL");
+  k.no_tail_fold = flag("QTX_NO_TAIL_FOLD");
   k.decode_groups = (int)num("QTX_DECODE_GROUPS", 0);
   k.graph_steps = (int)num("QTX_GRAPH_STEPS", 0);
   k.ws_min_m = num("QTX_WS_MIN_M", 2048L);

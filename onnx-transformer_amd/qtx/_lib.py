@@ -100,6 +100,7 @@ SIGNATURES = {
     "qtx_greedy_decode_scored": (I32, [P, P, P, I32, I32, I32, I64, P, P, P, P, SZ, FP, P]),
     "qtx_generator_top2": (I32, [P, P, I32, P, P, P, SZ, P]),
     "qtx_decode_top2_embed": (I32, [P, P, I32, P, I64, P, P, P, P, P]),
+    "qtx_decode_generator": (I32, [P, P, I32, P, P, P]),
     "qtx_debug_nop": (I32, [P]),
     "qtx_debug_reload_knobs": (I32, []),
     "qtx_model_check": (I32, [P, P]),
