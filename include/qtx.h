@@ -246,6 +246,67 @@ int32_t qtx_greedy_decode_scored(const qtx_model* m, const int64_t* src,
                                  int64_t start, int64_t* ids, int64_t* top_ids, float* top_logp,
                                  void* ws, size_t ws_bytes, const qtx_fault* fault, void* stream);
 
+/* ---- KV-cached greedy decode with one DECODER fault, and its resume for sweeps ----
+ * The campaign's trial (parallelized_inject_onnx_transformer.py:536-740) corrupts only the
+ * decoder run of step i = fault_step (its target_inference_number - 1): that step's token and
+ * nothing else directly.  So steps 0 .. i run KV-cached and golden; step i's cached run is the
+ * campaign's golden run (its out_2) of the same prefix; the faulty token comes from ONE faulty
+ * full-prefix decoder pass over ids[:, :i+1] (the fault's row indexes the whole batch's
+ * [B * (i+1)] tokens; cross K/V rows: [B * S]) with the generator on each sentence's last
+ * row; steps > i run KV-cached from the faulty token.  The caches are append-only: row i was
+ * written from the golden input of step i, and the cached cross K/V stay golden.
+ *
+ * qtx_greedy_decode_dfault (:536-740): bit for bit the campaign loop's result.
+ *   Scored form (top_ids and top_logp given): ids, and every step's top 2 under the scored
+ *   decode's rules above; entry fault_step holds the faulty step's top 2.
+ *   Plain form (top_ids == top_logp == NULL): ids only; the faulty step's token follows the
+ *   plain rule (qtx_generator: first index of the maximum logp, platform logf), the cached
+ *   steps the plain decode's tail.
+ *   rec_ids int64 / rec_logp float [B, 2, 2] (both or neither; NULL allowed): [:, 0, :] the
+ *   golden and [:, 1, :] the faulty top 2 of the corrupted step (:711-740).
+ *   fault_step >= max_len - 1: the fault is never applied — a golden decode, rec_* untouched
+ *   (the fault's coordinates are then not checked).
+ *   Path selection as the plain and scored decode: unfused step; QTX_NO_GRAPH eager fused
+ *   steps; else fused steps captured at the device counter's position as graphs of
+ *   QTX_GRAPH_STEPS (default 8) steps and of one step, with graphs ending at the fault step;
+ *   QTX_DECODE_GROUPS / two sub-batches from B = 512 (the faulty pass runs once over the whole
+ *   batch after they join).  The tail is never folded into the next step's first launch here.
+ *   Refused before anything is launched: fault NULL, kind NONE or module != 1, fault_step < 0,
+ *   a coordinate outside the step's shapes (T = fault_step + 1): QTX_E_INVALID; 4-bit weights:
+ *   QTX_E_UNSUPPORTED.  B * tgt_vocab and B * max_len * d_model below 2^30.
+ *   Writes exactly ids, top_ids, top_logp, rec_ids, rec_logp.  ws:
+ *   qtx_greedy_dfault_workspace_size bytes.
+ *
+ * qtx_greedy_dfault_resume (:536-740, one more trial on the same sentences): runs on a
+ * workspace a SCORED qtx_greedy_decode_dfault or an earlier resume left, for the same
+ * (m, B, S, max_len, src); scored outputs as above.  The library keeps a validity header per
+ * workspace in a HOST-side table of the model, keyed by the workspace pointer: the shapes, the
+ * highest step n up to which cache rows and ids are golden, and whether the workspace's second
+ * copy of the golden ids / top 2 is complete (it is after a never-applied decode).  Header
+ * missing or other shapes, or fault_step > n: QTX_E_INVALID.  Any other qtx call given that
+ * workspace drops the header, and the header's nonce is also stamped into the workspace and
+ * compared (one 8-byte copy) before a resume launches anything: memory that was overwritten
+ * since is refused (QTX_E_INVALID) where the stamp shows it.  The caller must not write it.
+ *   The faulty pass runs at fault_step from the golden prefix, the record is written, and the
+ *   per-sentence "token changed" flags are copied to changed_host[B] (may be NULL) — one small
+ *   synchronising copy.  No token changed and the golden copy complete: the outputs are the
+ *   golden decode's with entry fault_step replaced by the faulty top 2; no step runs, n stays.
+ *   Otherwise steps fault_step+1 .. run KV-cached from the faulty tokens, overwriting cache
+ *   rows and ids above fault_step, and n becomes fault_step.  A sweep that visits its trials
+ *   in DESCENDING step order therefore always finds its prefix golden. */
+size_t qtx_greedy_dfault_workspace_size(const qtx_model* m, int32_t B, int32_t S,
+                                        int32_t max_len);
+int32_t qtx_greedy_decode_dfault(const qtx_model* m, const int64_t* src, const uint8_t* src_mask,
+                                 int32_t B, int32_t S, int32_t max_len, int64_t start,
+                                 int64_t* ids, int64_t* top_ids, float* top_logp,
+                                 int64_t* rec_ids, float* rec_logp, void* ws, size_t ws_bytes,
+                                 const qtx_fault* fault, int32_t fault_step, void* stream);
+int32_t qtx_greedy_dfault_resume(const qtx_model* m, int32_t B, int32_t S, int32_t max_len,
+                                 int64_t* ids, int64_t* top_ids, float* top_logp,
+                                 int64_t* rec_ids, float* rec_logp, void* ws, size_t ws_bytes,
+                                 const qtx_fault* fault, int32_t fault_step,
+                                 int32_t* changed_host, void* stream);
+
 /* Embeddings + positional encoding: which = 0 (src) / 1 (tgt); ids int64 [B,T] ->
  * out [B,T,d], positions pos0 .. pos0+T-1. */
 int32_t qtx_embed(const qtx_model* m, int32_t which, const int64_t* ids, int32_t B, int32_t T,

@@ -142,6 +142,17 @@ struct qtx_model {
   hipStream_t gstream[QTX_MAX_GROUPS] = {};
   hipEvent_t ev_in = nullptr, ev_out[QTX_MAX_GROUPS] = {};
   std::map<GraphKey, GraphEntry> graphs;
+  // validity headers of the decoder-fault decode's workspaces, by workspace pointer (guarded
+  // by mu; include/qtx.h qtx_greedy_dfault_resume)
+  struct DfaultHdr {
+    int B, S, L;         // the shapes the workspace was filled for
+    int n;               // cache rows and ids of steps 0 .. n are golden
+    bool gold_full;      // the golden copies hold a whole golden decode
+    size_t bytes;
+    long long nonce;     // also stamped into the workspace: memory reused or overwritten by
+                         // someone else no longer matches
+  };
+  std::map<const void*, DfaultHdr> dfault;
   // encoder sub-batch pipelining: second stream + fork/lag/join events (lazily created)
   hipStream_t estream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_lag = nullptr, ev_join = nullptr;
@@ -166,6 +177,13 @@ struct qtx_model {
 };
 
 namespace {
+// A call that rewrites a workspace drops the decoder-fault decode's header for it: a later
+// qtx_greedy_dfault_resume on that memory is refused.
+void dfault_forget(const qtx_model* mc, const void* ws) {
+  qtx_model* m = const_cast<qtx_model*>(mc);
+  std::lock_guard<std::mutex> lk(m->mu);
+  m->dfault.erase(ws);
+}
 // Makes the model's device current for the lifetime of the guard (streams and events are
 // created on the current device), restoring the caller's device afterwards.
 struct DeviceGuard {
@@ -1245,6 +1263,9 @@ struct GreedyWS {
   // step; copied out to the caller's top_ids / top_logp
   int64_t* top_ids = nullptr;
   float* top_logp = nullptr;
+  // the decoder-fault decode (qtx_greedy_decode_dfault): its tail is never folded into the
+  // next step's first launch (a step may follow the faulty pass, not a generator launch)
+  bool no_fold = false;
 };
 
 // Sub-batch split of the fused decode.  Sentences are independent (per-token quantization:
@@ -1380,7 +1401,7 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
   // embeds it and stores ids / x itself (launch_skinny_tok) — a step is then 49 launches.
   // Only the last step still ends with the argmax kernel.
   const bool fold = !knobs().no_tail_fold && host_pos && !g.top_ids && wb == 8 && fused_ln &&
-                    !knobs().ablate && !knobs().dbg_tail;
+                    !knobs().ablate && !knobs().dbg_tail && !g.no_fold;
   Scratch& s = g.dec;
   // Timing experiments only (wrong results): QTX_ABLATE=<bitmask> drops kernel classes
   // from the step (replaced by an empty kernel with QTX_ABLATE_NOP=1) to measure what
@@ -1537,109 +1558,13 @@ int greedy_step_unfused(const qtx_model* m, GreedyWS& g, int B, int S, int max_l
 }
 
 
-int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S, int max_len,
-               int64_t start, const qtx_fault* f, hipStream_t st);
-
-}  // namespace
-
-extern "C" {
-
-size_t qtx_encoder_workspace_size(const qtx_model* m, int32_t B, int32_t S) {
-  return m ? enc_ws(m->cfg, B, S) : 0;
-}
-size_t qtx_decoder_workspace_size(const qtx_model* m, int32_t B, int32_t T, int32_t S) {
-  return m ? dec_ws(m->cfg, B, T, S) : 0;
-}
-size_t qtx_greedy_workspace_size(const qtx_model* m, int32_t B, int32_t S, int32_t max_len) {
-  if (!m) return 0;
-  Arena ar;
-  carve_greedy(ar, m->cfg, B, S, max_len);
-  return align_up(ar.used);
-}
-size_t qtx_greedy_scored_workspace_size(const qtx_model* m, int32_t B, int32_t S,
-                                        int32_t max_len) {
-  if (!m || max_len < 1) return 0;
-  Arena ar;
-  carve_greedy(ar, m->cfg, B, S, max_len, true);
-  return align_up(ar.used);
-}
-
-int32_t qtx_encoder_forward_fault(const qtx_model* m, const float* x, const uint8_t* src_mask,
-                                  int32_t B, int32_t S, float* out, void* ws, size_t ws_bytes,
-                                  const qtx_fault* f, void* stream) {
-  if (!m || !x || !src_mask || !out || !ws) return fail(QTX_E_INVALID, "null argument");
-  if (B <= 0 || S <= 0 || S > 512) return fail(QTX_E_INVALID, "bad shape B=%d S=%d", B, S);
-  if (ws_bytes < enc_ws(m->cfg, B, S)) return fail(QTX_E_WORKSPACE, "workspace too small");
-  RC(check_fault(m, f, 0, B, S, 0));
-  Arena ar;
-  ar.base = (uint8_t*)ws; ar.cap = ws_bytes;
-  hipStream_t st = (hipStream_t)stream;
-  unsigned* cst = nullptr;
-  RC(call_status_begin(m, &cst, st));
-  if (!enc_split(B) || (f && f->kind != QTX_FAULT_NONE)) {
-    Scratch s = carve_scratch(ar, m->cfg, (long)B * S);
-    s.status = cst;
-    return encoder_run(m, x, src_mask, B, S, out, s, st, f);
-  }
-  // The model's second stream and its three events are shared by every caller: the lock
-  // is held across the whole record / wait sequence, so two threads' fork, lag and join
-  // records cannot interleave (a wait always pairs with its own call's record).
-  qtx_model* mm = const_cast<qtx_model*>(m);
-  std::lock_guard<std::mutex> lk(mm->mu);
-  DeviceGuard dg(mm->device);
-  if (!mm->estream) {
-    HIPCHK(hipStreamCreateWithFlags(&mm->estream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&mm->ev_fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&mm->ev_lag, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&mm->ev_join, hipEventDisableTiming));
-  }
-  const int B0 = B / 2, B1 = B - B0;
-  const long D = m->cfg.d_model;
-  Scratch s0 = carve_scratch(ar, m->cfg, (long)B0 * S);
-  Scratch s1 = carve_scratch(ar, m->cfg, (long)B1 * S);
-  s0.status = s1.status = cst;
-  // half 1 starts when half 0's first layer has passed its QKV GEMM (ev_lag)
-  HIPCHK(hipEventRecord(mm->ev_fork, st));
-  HIPCHK(hipStreamWaitEvent(mm->estream, mm->ev_fork, 0));
-  RC(encoder_run(m, x, src_mask, B0, S, out, s0, st, nullptr, mm->ev_lag));
-  HIPCHK(hipStreamWaitEvent(mm->estream, mm->ev_lag, 0));
-  RC(encoder_run(m, x + (long)B0 * S * D, src_mask + (long)B0 * S, B1, S, out + (long)B0 * S * D,
-                 s1, mm->estream, nullptr));
-  HIPCHK(hipEventRecord(mm->ev_join, mm->estream));
-  HIPCHK(hipStreamWaitEvent(st, mm->ev_join, 0));
-  return QTX_OK;
-}
-
-int32_t qtx_encoder_forward(const qtx_model* m, const float* x, const uint8_t* src_mask,
-                            int32_t B, int32_t S, float* out, void* ws, size_t ws_bytes,
-                            void* stream) {
-  return qtx_encoder_forward_fault(m, x, src_mask, B, S, out, ws, ws_bytes, nullptr, stream);
-}
-
-int32_t qtx_decoder_forward_fault(const qtx_model* m, const float* y, const float* memory,
-                                  const uint8_t* src_mask, const uint8_t* tgt_mask,
-                                  int32_t tgt_mask_batched, int32_t B, int32_t T, int32_t S,
-                                  float* out, void* ws, size_t ws_bytes, const qtx_fault* f,
-                                  void* stream) {
-  if (!m || !y || !memory || !src_mask || !tgt_mask || !out || !ws)
-    return fail(QTX_E_INVALID, "null argument");
-  if (B <= 0 || T <= 0 || S <= 0 || T > 512 || S > 512)
-    return fail(QTX_E_INVALID, "bad shape B=%d T=%d S=%d", B, T, S);
-  if (ws_bytes < dec_ws(m->cfg, B, T, S)) return fail(QTX_E_WORKSPACE, "workspace too small");
-  RC(check_fault(m, f, 1, B, T, S));
-  hipStream_t st = (hipStream_t)stream;
+// The decoder stack over M = B * T rows: s.x holds the embedded targets, x the cross K/V
+// (cross_kv); out [M, D] = the final LayerNorm's output.  f: one optional fault.
+int decoder_body(const qtx_model* m, Scratch& s, const CrossKV& x, const uint8_t* src_mask,
+                 const uint8_t* tgt_mask, long tm_bs, int B, int T, int S, float* out,
+                 const qtx_fault* f, hipStream_t st) {
   const qtx_config& c = m->cfg;
   const int D = c.d_model, M = B * T;
-  // no decoder kernel sets a status word (the in-launch FFN1 exchange runs on the KP
-  // encoder path only), so this call neither claims nor touches the thread's word: an
-  // error an earlier encode left there stays until qtx_model_check reports it (ADVICE r04)
-  Arena ar;
-  ar.base = (uint8_t*)ws; ar.cap = ws_bytes;
-  Scratch s = carve_scratch(ar, c, M);
-  CrossKV x = carve_cross(ar, c, (long)B * S);
-  RC(cross_kv(m, memory, B * S, x, st, f));
-  HIPCHK(hipMemcpyAsync(s.x, y, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
-  const long tm_bs = tgt_mask_batched ? (long)T * T : 0;
   if (!row_path(c)) {
     for (int l = 0; l < c.n_layers; ++l) {
       const DecLayer& L = m->dec[l];
@@ -1701,6 +1626,114 @@ int32_t qtx_decoder_forward_fault(const qtx_model* m, const float* y, const floa
       RC(row_res_ln(L.w2, s.h8, s.sh, M, s.x, m->dec_norm, nullptr, nullptr, out, st, fa(G_FFN2)));
   }
   return QTX_OK;
+}
+
+int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S, int max_len,
+               int64_t start, const qtx_fault* f, hipStream_t st);
+
+}  // namespace
+
+extern "C" {
+
+size_t qtx_encoder_workspace_size(const qtx_model* m, int32_t B, int32_t S) {
+  return m ? enc_ws(m->cfg, B, S) : 0;
+}
+size_t qtx_decoder_workspace_size(const qtx_model* m, int32_t B, int32_t T, int32_t S) {
+  return m ? dec_ws(m->cfg, B, T, S) : 0;
+}
+size_t qtx_greedy_workspace_size(const qtx_model* m, int32_t B, int32_t S, int32_t max_len) {
+  if (!m) return 0;
+  Arena ar;
+  carve_greedy(ar, m->cfg, B, S, max_len);
+  return align_up(ar.used);
+}
+size_t qtx_greedy_scored_workspace_size(const qtx_model* m, int32_t B, int32_t S,
+                                        int32_t max_len) {
+  if (!m || max_len < 1) return 0;
+  Arena ar;
+  carve_greedy(ar, m->cfg, B, S, max_len, true);
+  return align_up(ar.used);
+}
+
+int32_t qtx_encoder_forward_fault(const qtx_model* m, const float* x, const uint8_t* src_mask,
+                                  int32_t B, int32_t S, float* out, void* ws, size_t ws_bytes,
+                                  const qtx_fault* f, void* stream) {
+  if (!m || !x || !src_mask || !out || !ws) return fail(QTX_E_INVALID, "null argument");
+  if (B <= 0 || S <= 0 || S > 512) return fail(QTX_E_INVALID, "bad shape B=%d S=%d", B, S);
+  if (ws_bytes < enc_ws(m->cfg, B, S)) return fail(QTX_E_WORKSPACE, "workspace too small");
+  RC(check_fault(m, f, 0, B, S, 0));
+  dfault_forget(m, ws);
+  Arena ar;
+  ar.base = (uint8_t*)ws; ar.cap = ws_bytes;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned* cst = nullptr;
+  RC(call_status_begin(m, &cst, st));
+  if (!enc_split(B) || (f && f->kind != QTX_FAULT_NONE)) {
+    Scratch s = carve_scratch(ar, m->cfg, (long)B * S);
+    s.status = cst;
+    return encoder_run(m, x, src_mask, B, S, out, s, st, f);
+  }
+  // The model's second stream and its three events are shared by every caller: the lock
+  // is held across the whole record / wait sequence, so two threads' fork, lag and join
+  // records cannot interleave (a wait always pairs with its own call's record).
+  qtx_model* mm = const_cast<qtx_model*>(m);
+  std::lock_guard<std::mutex> lk(mm->mu);
+  DeviceGuard dg(mm->device);
+  if (!mm->estream) {
+    HIPCHK(hipStreamCreateWithFlags(&mm->estream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&mm->ev_fork, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&mm->ev_lag, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&mm->ev_join, hipEventDisableTiming));
+  }
+  const int B0 = B / 2, B1 = B - B0;
+  const long D = m->cfg.d_model;
+  Scratch s0 = carve_scratch(ar, m->cfg, (long)B0 * S);
+  Scratch s1 = carve_scratch(ar, m->cfg, (long)B1 * S);
+  s0.status = s1.status = cst;
+  // half 1 starts when half 0's first layer has passed its QKV GEMM (ev_lag)
+  HIPCHK(hipEventRecord(mm->ev_fork, st));
+  HIPCHK(hipStreamWaitEvent(mm->estream, mm->ev_fork, 0));
+  RC(encoder_run(m, x, src_mask, B0, S, out, s0, st, nullptr, mm->ev_lag));
+  HIPCHK(hipStreamWaitEvent(mm->estream, mm->ev_lag, 0));
+  RC(encoder_run(m, x + (long)B0 * S * D, src_mask + (long)B0 * S, B1, S, out + (long)B0 * S * D,
+                 s1, mm->estream, nullptr));
+  HIPCHK(hipEventRecord(mm->ev_join, mm->estream));
+  HIPCHK(hipStreamWaitEvent(st, mm->ev_join, 0));
+  return QTX_OK;
+}
+
+int32_t qtx_encoder_forward(const qtx_model* m, const float* x, const uint8_t* src_mask,
+                            int32_t B, int32_t S, float* out, void* ws, size_t ws_bytes,
+                            void* stream) {
+  return qtx_encoder_forward_fault(m, x, src_mask, B, S, out, ws, ws_bytes, nullptr, stream);
+}
+
+int32_t qtx_decoder_forward_fault(const qtx_model* m, const float* y, const float* memory,
+                                  const uint8_t* src_mask, const uint8_t* tgt_mask,
+                                  int32_t tgt_mask_batched, int32_t B, int32_t T, int32_t S,
+                                  float* out, void* ws, size_t ws_bytes, const qtx_fault* f,
+                                  void* stream) {
+  if (!m || !y || !memory || !src_mask || !tgt_mask || !out || !ws)
+    return fail(QTX_E_INVALID, "null argument");
+  if (B <= 0 || T <= 0 || S <= 0 || T > 512 || S > 512)
+    return fail(QTX_E_INVALID, "bad shape B=%d T=%d S=%d", B, T, S);
+  if (ws_bytes < dec_ws(m->cfg, B, T, S)) return fail(QTX_E_WORKSPACE, "workspace too small");
+  RC(check_fault(m, f, 1, B, T, S));
+  dfault_forget(m, ws);
+  hipStream_t st = (hipStream_t)stream;
+  const qtx_config& c = m->cfg;
+  const int D = c.d_model, M = B * T;
+  // no decoder kernel sets a status word (the in-launch FFN1 exchange runs on the KP
+  // encoder path only), so this call neither claims nor touches the thread's word: an
+  // error an earlier encode left there stays until qtx_model_check reports it (ADVICE r04)
+  Arena ar;
+  ar.base = (uint8_t*)ws; ar.cap = ws_bytes;
+  Scratch s = carve_scratch(ar, c, M);
+  CrossKV x = carve_cross(ar, c, (long)B * S);
+  RC(cross_kv(m, memory, B * S, x, st, f));
+  HIPCHK(hipMemcpyAsync(s.x, y, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
+  return decoder_body(m, s, x, src_mask, tgt_mask, tgt_mask_batched ? (long)T * T : 0, B, T, S, out,
+                      f, st);
 }
 
 int32_t qtx_decoder_forward(const qtx_model* m, const float* y, const float* memory,
@@ -1774,6 +1807,7 @@ static int32_t greedy_decode(const qtx_model* m, const int64_t* src, const uint8
     return fail(QTX_E_UNSUPPORTED, "greedy decode takes encoder faults (decoder faults: "
                                    "qtx_decoder_forward_fault on the step's prefix)");
   RC(check_fault(m, f, 0, B, S, 0));
+  dfault_forget(m, ws);
   hipStream_t st = (hipStream_t)stream;
   Arena ar;
   ar.base = (uint8_t*)ws; ar.cap = ws_bytes;
@@ -1839,14 +1873,18 @@ int32_t qtx_greedy_decode(const qtx_model* m, const int64_t* src, const uint8_t*
 
 namespace {
 
-int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S, int max_len,
-               int64_t start, const qtx_fault* f, hipStream_t st) {
+// whether the decode runs the fused step (else the unfused one)
+bool greedy_fused(const qtx_config& c, int S, int max_len) {
+  return S <= 128 && max_len <= 128 && fused_step_ok(c) && !knobs().unfused;
+}
+
+// What precedes the steps: the encoder, the cross K/V, ids[:, 0] and the step counters.
+int greedy_prologue(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S,
+                    int max_len, int64_t start, const qtx_fault* f, bool fused, hipStream_t st) {
   const qtx_config& c = m->cfg;
   const int D = c.d_model;
   const uint8_t* src_mask = g.mask;
   int64_t* ids = g.ids;
-  const bool fused = S <= 128 && max_len <= 128 && fused_step_ok(c) && !knobs().unfused;
-
   // encoder: memory = encode(src_embed(src), src_mask); the cross K/V of every layer
   // (captured into a hipGraph with the steps' replay — QTX_PRE_GRAPH in round 3 — it
   // measured no faster: 14.34 vs 14.31 ms per B = 32 decode; the host's enqueue of these
@@ -1864,6 +1902,17 @@ int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S
   // ids[:, 0] = start ; step[0] = position 0, step[1] = arrival counter
   HIPCHK(launch_fill_col(ids, max_len, B, start, st));
   HIPCHK(launch_zero(g.step, 16, st));
+  return QTX_OK;
+}
+
+int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S, int max_len,
+               int64_t start, const qtx_fault* f, hipStream_t st) {
+  const qtx_config& c = m->cfg;
+  const int D = c.d_model;
+  const uint8_t* src_mask = g.mask;
+  int64_t* ids = g.ids;
+  const bool fused = greedy_fused(c, S, max_len);
+  RC(greedy_prologue(m, g, src, B, S, max_len, start, f, fused, st));
   if (!fused) {
     for (int t = 0; t + 1 < max_len; ++t) RC(greedy_step_unfused(m, g, B, S, max_len, ids, src_mask, st));
     return QTX_OK;
@@ -2024,6 +2073,401 @@ int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S
 }
 
 }  // namespace
+
+// =======================================================================================
+// KV-cached greedy decode with one decoder fault (include/qtx.h: qtx_greedy_decode_dfault)
+// =======================================================================================
+namespace {
+
+// The workspace: the scored decode's (a prefix, so the captured steps see the same buffers
+// in the plain and the scored form), then the faulty pass's scratch, the record, and the
+// golden copies a resume returns.
+struct DfaultWS {
+  GreedyWS g;
+  Scratch fs;           // the faulty full-prefix pass, B * (max_len - 1) rows
+  CrossKV fx;           // its cross K/V when the fault sits in a memory K/V projection
+  float* fout;          // [B * (max_len - 1), D] its output
+  float* flogits;       // [B, V] the generator on each sentence's last row
+  uint8_t* tmask;       // [T, T] causal mask
+  int64_t* rec_ids;     // [B, 2, 2]
+  float* rec_logp;
+  int* changed;         // [B]
+  int64_t* gold_ids;    // [B, max_len]          the golden decode, as far as it is known
+  int64_t* gold_top_ids;   // [B, max_len-1, 2]  (qtx_model::DfaultHdr)
+  float* gold_top_logp;
+  int64_t* stamp;       // [2] the header's nonce (resume compares it with the host table's)
+};
+
+DfaultWS carve_dfault(Arena& ar, const qtx_config& c, int B, int S, int max_len) {
+  DfaultWS w;
+  const size_t D = c.d_model, Tm = max_len > 1 ? max_len - 1 : 1;
+  w.g = carve_greedy(ar, c, B, S, max_len, true);
+  w.g.no_fold = true;
+  w.fs = carve_scratch(ar, c, (long)(B * Tm));
+  w.fx = carve_cross(ar, c, (long)B * S);
+  w.fout = ar.take<float>(B * Tm * D);
+  w.flogits = ar.take<float>((size_t)B * c.tgt_vocab);
+  w.tmask = ar.take<uint8_t>(Tm * Tm);
+  w.rec_ids = ar.take<int64_t>((size_t)B * 4);
+  w.rec_logp = ar.take<float>((size_t)B * 4);
+  w.changed = ar.take<int>((size_t)B);
+  w.gold_ids = ar.take<int64_t>((size_t)B * max_len);
+  w.gold_top_ids = ar.take<int64_t>(B * Tm * 2);
+  w.gold_top_logp = ar.take<float>(B * Tm * 2);
+  w.stamp = ar.take<int64_t>(2);
+  return w;
+}
+
+size_t dfault_ws(const qtx_config& c, int B, int S, int max_len) {
+  Arena ar;
+  carve_dfault(ar, c, B, S, max_len);
+  return align_up(ar.used);
+}
+
+// KV-cached steps t0 .. t1-1 from ids[:, t0], with the decode's path selection: the unfused
+// step; the fused step launched eagerly at host positions (QTX_NO_GRAPH); or the fused step
+// captured at the device counter's position — graphs of QTX_GRAPH_STEPS (default 8) steps and
+// of one step, so that any range is a few replays and a sweep over fault steps captures
+// nothing new.  A range never crosses the fault step: the caller splits there.
+int dfault_steps(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, int t0, int t1,
+                 hipStream_t st) {
+  if (t0 >= t1) return QTX_OK;
+  const qtx_config& c = m->cfg;
+  const int D = c.d_model;
+  const bool fused = greedy_fused(c, S, max_len);
+  const Groups gr = decode_groups(B);
+  HIPCHK(launch_set_steps(g.step, g.gsteps, fused ? gr.G : 0, t0, st));
+  if (!fused) {
+    for (int t = t0; t < t1; ++t) RC(greedy_step_unfused(m, g, B, S, max_len, g.ids, g.mask, st));
+    return QTX_OK;
+  }
+  std::vector<GreedyWS> gv;
+  for (int i = 0; i < gr.G; ++i) {   // the first decoder input: tgt_embed(ids[:, t0]) at t0
+    gv.push_back(group_view(g, c, i, gr.b0(i), S, max_len));
+    HIPCHK(launch_embed(g.ids + (long)gr.b0(i) * max_len + t0, max_len, gr.rows(i, B), 1, nullptr,
+                        t0, m->tgt_lut, c.tgt_vocab, m->pe, c.max_len, gv[i].dec.x, D, st));
+  }
+  auto step_fn = [&](int i, hipStream_t s, int t) {
+    return greedy_step_fused(m, gv[i], gr.rows(i, B), S, max_len, g.ids + (long)gr.b0(i) * max_len,
+                             g.mask + (long)gr.b0(i) * S, s, t);
+  };
+  qtx_model* mm = const_cast<qtx_model*>(m);
+  std::lock_guard<std::mutex> lock(mm->mu);
+  DeviceGuard dg(mm->device);
+  if (!mm->ev_in) HIPCHK(hipEventCreateWithFlags(&mm->ev_in, hipEventDisableTiming));
+  for (int i = 0; i < gr.G; ++i)
+    if (!mm->gstream[i]) {
+      HIPCHK(hipStreamCreateWithFlags(&mm->gstream[i], hipStreamNonBlocking));
+      HIPCHK(hipEventCreateWithFlags(&mm->ev_out[i], hipEventDisableTiming));
+    }
+  const bool fork = gr.G > 1;
+  hipStream_t ls[QTX_MAX_GROUPS];
+  for (int i = 0; i < gr.G; ++i) ls[i] = fork ? mm->gstream[i] : st;
+  auto fork_in = [&]() -> int {
+    if (!fork) return QTX_OK;
+    HIPCHK(hipEventRecord(mm->ev_in, st));
+    for (int i = 0; i < gr.G; ++i) HIPCHK(hipStreamWaitEvent(ls[i], mm->ev_in, 0));
+    return QTX_OK;
+  };
+  auto join_out = [&]() -> int {
+    if (!fork) return QTX_OK;
+    for (int i = 0; i < gr.G; ++i) {
+      HIPCHK(hipEventRecord(mm->ev_out[i], ls[i]));
+      HIPCHK(hipStreamWaitEvent(st, mm->ev_out[i], 0));
+    }
+    return QTX_OK;
+  };
+  if (knobs().no_graph) {
+    RC(fork_in());
+    for (int t = t0; t < t1; ++t)
+      for (int i = 0; i < gr.G; ++i) RC(step_fn(i, ls[i], t));
+    return join_out();
+  }
+  const int big = knobs().graph_steps > 0 ? knobs().graph_steps : 8;
+  const Knobs& kn = knobs();
+  const std::string variant = std::to_string(knobs_generation()) + ":" + std::to_string(kn.split_ln) +
+                              std::to_string(kn.ffn_qkernel) + std::to_string(kn.device_step) +
+                              (g.top_ids ? "ds" : "d");   // this entry's own graphs
+  auto key_of = [&](int per) { return GraphKey{B, S, max_len, gr.G * 1000 + per, g.gsteps, variant}; };
+  // one graph of `per` steps per sub-batch, captured on first use
+  auto ensure = [&](int per) -> int {
+    if (mm->graphs.find(key_of(per)) != mm->graphs.end()) return QTX_OK;
+    if (mm->graphs.size() >= 16) mm->clear_graphs();
+    std::vector<hipGraphExec_t> execs;
+    auto drop = [&] {
+      for (hipGraphExec_t e : execs) (void)hipGraphExecDestroy(e);
+    };
+    for (int i = 0; i < gr.G; ++i) {
+      hipGraph_t graph = nullptr;
+      hipError_t e = hipStreamBeginCapture(mm->gstream[i], hipStreamCaptureModeThreadLocal);
+      if (e != hipSuccess) { drop(); HIPCHK(e); }
+      int rc = QTX_OK;
+      for (int t = 0; t < per && rc == QTX_OK; ++t) rc = step_fn(i, mm->gstream[i], -1);
+      e = hipStreamEndCapture(mm->gstream[i], &graph);
+      if (rc != QTX_OK || e != hipSuccess) {
+        if (graph) (void)hipGraphDestroy(graph);
+        drop();
+        if (rc != QTX_OK) return rc;
+        HIPCHK(e);
+      }
+      hipGraphExec_t exec = nullptr;
+      e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+      (void)hipGraphDestroy(graph);
+      if (e != hipSuccess) { drop(); HIPCHK(e); }
+      execs.push_back(exec);
+    }
+    GraphEntry ent;
+    ent.execs = std::move(execs);
+    mm->graphs.emplace(key_of(per), std::move(ent));
+    return QTX_OK;
+  };
+  const int nbig = big > 1 ? (t1 - t0) / big : 0, none = (t1 - t0) - nbig * big;
+  for (int pass = 0; pass < 2; ++pass) {   // (a capture may clear the cache: look again)
+    if (nbig) RC(ensure(big));
+    if (none) RC(ensure(1));
+  }
+  std::vector<std::pair<int, int>> plan;   // (steps per graph, replays)
+  if (nbig) plan.push_back({big, nbig});
+  if (none) plan.push_back({1, none});
+  for (const auto& pr : plan)
+    if (mm->graphs.find(key_of(pr.first)) == mm->graphs.end())
+      return fail(QTX_E_HIP, "decode graph missing");
+  RC(fork_in());
+  for (const auto& pr : plan) {
+    auto it = mm->graphs.find(key_of(pr.first));
+    for (int r = 0; r < pr.second; ++r)
+      for (int i = 0; i < gr.G; ++i) HIPCHK(hipGraphLaunch(it->second.execs[i], ls[i]));
+  }
+  RC(join_out());
+  for (const auto& pr : plan) {   // completion markers (after the join: every sub-batch)
+    auto it = mm->graphs.find(key_of(pr.first));
+    if (!it->second.done) HIPCHK(hipEventCreateWithFlags(&it->second.done, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(it->second.done, st));
+  }
+  return QTX_OK;
+}
+
+// The faulty full-prefix decoder pass of step `step` over the whole batch (the fault's row
+// indexes its [B * T] tokens, T = step + 1) and the generator on each sentence's last row:
+// flogits [B, V].  The body of qtx_decoder_forward_fault on this call's workspace; the
+// cached cross K/V are read, never written (a memory K/V fault gets its own copy).
+int dfault_pass(const qtx_model* m, DfaultWS& w, int B, int S, int max_len, const qtx_fault* f,
+                int step, hipStream_t st) {
+  const qtx_config& c = m->cfg;
+  const int D = c.d_model, T = step + 1;
+  GreedyWS& g = w.g;
+  // the scratch was carved for the longest prefix: the three projections and their scales lie
+  // M = B * T rows apart, as the row GEMM writes them (carve_scratch)
+  Scratch s = w.fs;
+  const long M = (long)B * T;
+  s.k8 = s.q8 + M * D; s.v8 = s.k8 + M * D;
+  s.sk = s.sq + M; s.sv = s.sk + M;
+  HIPCHK(launch_embed(g.ids, max_len, B, T, nullptr, 0, m->tgt_lut, c.tgt_vocab, m->pe, c.max_len,
+                      s.x, (long)T * D, st));
+  HIPCHK(launch_causal_mask(w.tmask, T, st));
+  bool ckv_fault = false;
+  for (int l = 0; l < c.n_layers; ++l)
+    ckv_fault |= fault_for(f, 1, l, G_CKV, B * S, c).kind != FK_NONE;
+  if (ckv_fault) RC(cross_kv(m, g.memory, B * S, w.fx, st, f));
+  RC(decoder_body(m, s, ckv_fault ? w.fx : g.cross, g.mask, w.tmask, 0, B, T, S, w.fout, f, st));
+  HIPCHK(launch_generator_mfma(w.fout + (long)(T - 1) * D, (long)T * D, B, nullptr, nullptr,
+                               m->gen_wt, m->gen_b, c.tgt_vocab, w.flogits, st));
+  return QTX_OK;
+}
+
+// the faulty top 2 into rec[:, 1, :]
+int dfault_top2(const qtx_model* m, DfaultWS& w, int B, hipStream_t st) {
+  HIPCHK(launch_logsoftmax_top2(w.flogits, B, m->cfg.tgt_vocab, nullptr, 0, nullptr, 0,
+                                w.rec_ids + 2, w.rec_logp + 2, 2, st));
+  return QTX_OK;
+}
+
+void dfault_store(const qtx_model* m, const void* ws, const qtx_model::DfaultHdr& h) {
+  qtx_model* mm = const_cast<qtx_model*>(m);
+  std::lock_guard<std::mutex> lk(mm->mu);
+  mm->dfault[ws] = h;
+}
+
+int dfault_args(const qtx_model* m, int B, int S, int max_len, const qtx_fault* f, int fault_step) {
+  const qtx_config& c = m->cfg;
+  if (B <= 0 || S <= 0 || S > 512 || max_len < 1 || max_len > 512 || max_len > c.max_len ||
+      S > c.max_len)
+    return fail(QTX_E_INVALID, "bad shape B=%d S=%d max_len=%d", B, S, max_len);
+  if ((long)B * c.tgt_vocab >= (1L << 30) || (long)B * max_len * c.d_model >= (1L << 30))
+    return fail(QTX_E_INVALID, "B * tgt_vocab and B * max_len * d_model must be below 2^30");
+  if (!f || f->kind == QTX_FAULT_NONE || f->module != 1)
+    return fail(QTX_E_INVALID, "the decoder-fault decode takes one decoder fault (encoder "
+                               "faults: qtx_greedy_decode_fault / _scored)");
+  if (fault_step < 0) return fail(QTX_E_INVALID, "fault_step %d", fault_step);
+  if (c.weight_bits != 8) return fail(QTX_E_UNSUPPORTED, "fault injection needs 8-bit weights");
+  if (knobs().dbg_tail) return fail(QTX_E_UNSUPPORTED, "decoder-fault decode: not with QTX_DBG_TAIL");
+  return QTX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t qtx_greedy_dfault_workspace_size(const qtx_model* m, int32_t B, int32_t S,
+                                        int32_t max_len) {
+  if (!m || B <= 0 || S <= 0 || max_len < 1) return 0;
+  return dfault_ws(m->cfg, B, S, max_len);
+}
+
+int32_t qtx_greedy_decode_dfault(const qtx_model* m, const int64_t* src, const uint8_t* src_mask,
+                                 int32_t B, int32_t S, int32_t max_len, int64_t start,
+                                 int64_t* ids, int64_t* top_ids, float* top_logp,
+                                 int64_t* rec_ids, float* rec_logp, void* ws, size_t ws_bytes,
+                                 const qtx_fault* f, int32_t fault_step, void* stream) {
+  if (!m || !src || !src_mask || !ids || !ws) return fail(QTX_E_INVALID, "null argument");
+  const bool scored = top_ids || top_logp;
+  if ((scored && (!top_ids || !top_logp)) || !rec_ids != !rec_logp)
+    return fail(QTX_E_INVALID, "top_ids / top_logp and rec_ids / rec_logp come in pairs");
+  RC(dfault_args(m, B, S, max_len, f, fault_step));
+  const qtx_config& c = m->cfg;
+  if ((scored || rec_ids) && c.tgt_vocab < 2)
+    return fail(QTX_E_INVALID, "top 2 needs tgt_vocab >= 2 (%d)", c.tgt_vocab);
+  if (ws_bytes < dfault_ws(c, B, S, max_len)) return fail(QTX_E_WORKSPACE, "workspace too small");
+  const int last = max_len - 1;             // steps 0 .. last-1
+  const bool applied = fault_step < last;   // else the fault's step is never run: golden
+  if (applied) RC(check_fault(m, f, 1, B, fault_step + 1, S));
+  hipStream_t st = (hipStream_t)stream;
+  dfault_forget(m, ws);                     // no header while the workspace is rewritten
+  Arena ar;
+  ar.base = (uint8_t*)ws; ar.cap = ws_bytes;
+  unsigned* cst = nullptr;
+  RC(call_status_begin(m, &cst, st));
+  DfaultWS w = carve_dfault(ar, c, B, S, max_len);
+  GreedyWS& g = w.g;
+  g.enc.status = cst;
+  if (!scored) g.top_ids = nullptr, g.top_logp = nullptr;   // the plain step and its tail
+  const size_t nid = (size_t)B * max_len * sizeof(int64_t), nt = (size_t)B * last * 2;
+  auto keep_gold = [&]() -> int {   // what is golden so far, for later resumes
+    HIPCHK(hipMemcpyAsync(w.gold_ids, g.ids, nid, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(w.gold_top_ids, g.top_ids, nt * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(w.gold_top_logp, g.top_logp, nt * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return QTX_OK;
+  };
+  HIPCHK(hipMemcpyAsync(g.mask, src_mask, (size_t)B * S, hipMemcpyDeviceToDevice, st));
+  RC(greedy_prologue(m, g, src, B, S, max_len, start, nullptr, greedy_fused(c, S, max_len), st));
+  RC(dfault_steps(m, g, B, S, max_len, 0, applied ? fault_step + 1 : last, st));
+  if (applied) {
+    const int V = c.tgt_vocab;
+    if (scored) {          // the cached step's top 2 is the golden record (the campaign's out_2)
+      RC(keep_gold());
+      HIPCHK(launch_dfault_gold(g.top_ids, g.top_logp, last, fault_step, B, w.rec_ids, w.rec_logp, st));
+    } else if (rec_ids) {  // plain form: from the cached step's logits
+      HIPCHK(launch_logsoftmax_top2(g.logits, B, V, nullptr, 0, nullptr, 0, w.rec_ids, w.rec_logp, 2, st));
+    }
+    RC(dfault_pass(m, w, B, S, max_len, f, fault_step, st));
+    if (scored || rec_ids) RC(dfault_top2(m, w, B, st));
+    if (scored)
+      HIPCHK(launch_dfault_tail(w.rec_ids, w.rec_logp, B, fault_step, max_len, g.ids, g.top_ids,
+                                g.top_logp, nullptr, st));
+    else                   // the plain tail's rule (qtx_generator without log-probabilities)
+      HIPCHK(launch_logsoftmax_argmax(w.flogits, B, V, nullptr, g.ids, max_len, nullptr,
+                                      fault_step + 1, st));
+    RC(dfault_steps(m, g, B, S, max_len, fault_step + 1, last, st));
+  } else if (scored && last > 0) {
+    RC(keep_gold());
+  }
+  HIPCHK(hipMemcpyAsync(ids, g.ids, nid, hipMemcpyDeviceToDevice, st));
+  if (scored && last > 0) {
+    HIPCHK(hipMemcpyAsync(top_ids, g.top_ids, nt * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(top_logp, g.top_logp, nt * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  if (applied && rec_ids) {
+    HIPCHK(hipMemcpyAsync(rec_ids, w.rec_ids, (size_t)B * 4 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(rec_logp, w.rec_logp, (size_t)B * 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  if (scored && last > 0) {
+    static std::atomic<long long> next_nonce{1};
+    const long long nonce = (long long)(m->serial << 40) ^ next_nonce.fetch_add(1);
+    HIPCHK(launch_fill_col(w.stamp, 1, 1, nonce, st));
+    dfault_store(m, ws, qtx_model::DfaultHdr{B, S, max_len, applied ? fault_step : last - 1,
+                                             !applied, ws_bytes, nonce});
+  }
+  return QTX_OK;
+}
+
+int32_t qtx_greedy_dfault_resume(const qtx_model* m, int32_t B, int32_t S, int32_t max_len,
+                                 int64_t* ids, int64_t* top_ids, float* top_logp,
+                                 int64_t* rec_ids, float* rec_logp, void* ws, size_t ws_bytes,
+                                 const qtx_fault* f, int32_t fault_step, int32_t* changed_host,
+                                 void* stream) {
+  if (!m || !ids || !top_ids || !top_logp || !ws || !rec_ids != !rec_logp)
+    return fail(QTX_E_INVALID, "null argument");
+  RC(dfault_args(m, B, S, max_len, f, fault_step));
+  const qtx_config& c = m->cfg;
+  if (c.tgt_vocab < 2) return fail(QTX_E_INVALID, "top 2 needs tgt_vocab >= 2 (%d)", c.tgt_vocab);
+  if (ws_bytes < dfault_ws(c, B, S, max_len)) return fail(QTX_E_WORKSPACE, "workspace too small");
+  qtx_model::DfaultHdr h{};
+  {
+    qtx_model* mm = const_cast<qtx_model*>(m);
+    std::lock_guard<std::mutex> lk(mm->mu);
+    auto it = mm->dfault.find(ws);
+    if (it == mm->dfault.end())
+      return fail(QTX_E_INVALID, "resume: the workspace holds no scored decoder-fault decode of this model");
+    h = it->second;
+  }
+  if (h.B != B || h.S != S || h.L != max_len)
+    return fail(QTX_E_INVALID, "resume: the workspace was filled for B=%d S=%d max_len=%d", h.B, h.S, h.L);
+  if (fault_step > h.n)
+    return fail(QTX_E_INVALID, "resume: fault_step %d above the golden prefix's last step %d",
+                fault_step, h.n);
+  RC(check_fault(m, f, 1, B, fault_step + 1, S));
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar;
+  ar.base = (uint8_t*)ws; ar.cap = ws_bytes;
+  DfaultWS w = carve_dfault(ar, c, B, S, max_len);
+  GreedyWS& g = w.g;
+  long long stamp = 0;   // the memory must still be what the header describes
+  HIPCHK(hipMemcpyAsync(&stamp, w.stamp, sizeof stamp, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (stamp != h.nonce) {
+    dfault_forget(m, ws);
+    return fail(QTX_E_INVALID, "resume: the workspace was overwritten since its decode");
+  }
+  const int last = max_len - 1;
+  const size_t nid = (size_t)B * max_len * sizeof(int64_t), nt = (size_t)B * last * 2;
+  HIPCHK(launch_dfault_gold(w.gold_top_ids, w.gold_top_logp, last, fault_step, B, w.rec_ids,
+                            w.rec_logp, st));
+  RC(dfault_pass(m, w, B, S, max_len, f, fault_step, st));
+  RC(dfault_top2(m, w, B, st));
+  HIPCHK(launch_dfault_tail(w.rec_ids, w.rec_logp, B, fault_step, max_len, nullptr, nullptr,
+                            nullptr, w.changed, st));
+  // the one synchronising copy: whether any sentence's token changed decides what runs next
+  std::vector<int32_t> changed((size_t)B);
+  HIPCHK(hipMemcpyAsync(changed.data(), w.changed, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  bool any = false;
+  for (int b = 0; b < B; ++b) any |= changed[b] != 0;
+  if (changed_host) std::copy(changed.begin(), changed.end(), changed_host);
+  if (!any && h.gold_full) {   // a masked fault: the golden decode with the faulty entry
+    HIPCHK(hipMemcpyAsync(ids, w.gold_ids, nid, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(top_ids, w.gold_top_ids, nt * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(top_logp, w.gold_top_logp, nt * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(launch_dfault_tail(w.rec_ids, w.rec_logp, B, fault_step, max_len, nullptr, top_ids,
+                              top_logp, nullptr, st));
+  } else {                     // the steps above fault_step again, from the faulty tokens
+    dfault_forget(m, ws);
+    HIPCHK(launch_dfault_tail(w.rec_ids, w.rec_logp, B, fault_step, max_len, g.ids, g.top_ids,
+                              g.top_logp, nullptr, st));
+    RC(dfault_steps(m, g, B, S, max_len, fault_step + 1, last, st));
+    HIPCHK(hipMemcpyAsync(ids, g.ids, nid, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(top_ids, g.top_ids, nt * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(top_logp, g.top_logp, nt * sizeof(float), hipMemcpyDeviceToDevice, st));
+    h.n = fault_step;
+    dfault_store(m, ws, h);
+  }
+  if (rec_ids) {
+    HIPCHK(hipMemcpyAsync(rec_ids, w.rec_ids, (size_t)B * 4 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(rec_logp, w.rec_logp, (size_t)B * 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  return QTX_OK;
+}
+
+}  // extern "C"
 
 extern "C" {
 

@@ -1829,4 +1829,93 @@ hipError_t launch_top2_embed(const float* logits, int M, int V, int64_t* ids, lo
   return hipGetLastError();
 }
 
+// =====================================================================================
+// The decoder-fault decode's small kernels (qtx_greedy_decode_dfault, qtx_api.hip): one lane
+// per sentence.  Scalars lead the parameter lists (preloaded); every offset is bounded on
+// the host (B * ids_bs < 2^30) and every position write checks its column.
+//   rec_ids int64 / rec_logp float [B][2][2]: [b][0] the golden, [b][1] the faulty top 2 of
+//   the corrupted step.
+// =====================================================================================
+// k_dfault_gold: rec[b][0][:] = entry (b, step) of top_ids / top_logp [B][top_bs][2] — the
+// golden pair, kept before the faulty one replaces the entry
+__global__ __launch_bounds__(64) void k_dfault_gold(int B, int step, int top_bs,
+                                                    const int64_t* top_ids, const float* top_logp,
+                                                    int64_t* rec_ids, float* rec_logp) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B || step >= top_bs) return;
+  const int e = 2 * (b * top_bs + step);
+  rec_ids[4 * b] = top_ids[e]; rec_ids[4 * b + 1] = top_ids[e + 1];
+  rec_logp[4 * b] = top_logp[e]; rec_logp[4 * b + 1] = top_logp[e + 1];
+}
+
+hipError_t launch_dfault_gold(const int64_t* top_ids, const float* top_logp, long top_bs,
+                              int step, int B, int64_t* rec_ids, float* rec_logp,
+                              hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (step < 0 || step >= top_bs || (long)B * top_bs >= (1L << 29)) return hipErrorInvalidValue;
+  k_dfault_gold<<<dim3((B + 63) / 64), dim3(64), 0, st>>>(B, step, (int)top_bs, top_ids, top_logp,
+                                                         rec_ids, rec_logp);
+  return hipGetLastError();
+}
+
+// k_dfault_tail: the faulty pair rec[b][1][:] goes out — its winner to ids[b][step + 1], the
+// pair to entry (b, step) of top_ids / top_logp [B][ids_bs - 1][2], and changed[b] = (the
+// golden winner != the faulty one).  ids, top_ids / top_logp, changed: each may be null.
+__global__ __launch_bounds__(64) void k_dfault_tail(int B, int step, int ids_bs,
+                                                    const int64_t* rec_ids, const float* rec_logp,
+                                                    int64_t* ids, int64_t* top_ids,
+                                                    float* top_logp, int* changed) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const int64_t f0 = rec_ids[4 * b + 2], f1 = rec_ids[4 * b + 3];
+  if (ids && step + 1 < ids_bs) ids[b * ids_bs + step + 1] = f0;
+  if (top_ids && step < ids_bs - 1) {
+    const int e = 2 * (b * (ids_bs - 1) + step);
+    top_ids[e] = f0; top_ids[e + 1] = f1;
+    top_logp[e] = rec_logp[4 * b + 2]; top_logp[e + 1] = rec_logp[4 * b + 3];
+  }
+  if (changed) changed[b] = rec_ids[4 * b] != f0 ? 1 : 0;
+}
+
+hipError_t launch_dfault_tail(const int64_t* rec_ids, const float* rec_logp, int B, int step,
+                              long ids_bs, int64_t* ids, int64_t* top_ids, float* top_logp,
+                              int* changed, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (step < 0 || step + 1 >= ids_bs || (long)B * ids_bs >= (1L << 29) || !top_ids != !top_logp)
+    return hipErrorInvalidValue;
+  k_dfault_tail<<<dim3((B + 63) / 64), dim3(64), 0, st>>>(B, step, (int)ids_bs, rec_ids, rec_logp,
+                                                         ids, top_ids, top_logp, changed);
+  return hipGetLastError();
+}
+
+// k_causal_mask: mask [T][T] uint8, keep[i][j] = j <= i (the faulty pass's target mask)
+__global__ __launch_bounds__(256) void k_causal_mask(int T, uint8_t* mask) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= T * T) return;
+  mask[e] = e % T <= e / T ? 1 : 0;
+}
+
+hipError_t launch_causal_mask(uint8_t* mask, int T, hipStream_t st) {
+  if (T <= 0) return hipSuccess;
+  if (T > 512) return hipErrorInvalidValue;
+  k_causal_mask<<<dim3((T * T + 255) / 256), dim3(256), 0, st>>>(T, mask);
+  return hipGetLastError();
+}
+
+// k_set_steps: the decode's position counters set to `value`, the arrival counters to 0:
+// step [4] (the unfused step) and the G sub-batches' gsteps [G][4] (lane g + 1)
+__global__ __launch_bounds__(64) void k_set_steps(int G, int value, int* step, int* gsteps) {
+  const int l = threadIdx.x;
+  if (l > G) return;
+  int* s = l == 0 ? step : gsteps + 4 * (l - 1);
+  s[0] = value;
+  s[1] = 0;
+}
+
+hipError_t launch_set_steps(int* step, int* gsteps, int G, int value, hipStream_t st) {
+  if (G < 0 || G > 63 || value < 0) return hipErrorInvalidValue;
+  k_set_steps<<<dim3(1), dim3(64), 0, st>>>(G, value, step, gsteps);
+  return hipGetLastError();
+}
+
 }  // namespace qtx

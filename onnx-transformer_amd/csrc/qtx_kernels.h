@@ -266,6 +266,21 @@ hipError_t launch_top2_embed(const float* logits, int M, int V, int64_t* ids, lo
                              int64_t* top_ids, float* top_logp, int* step, unsigned* arrive,
                              const float* lut, const float* pe, int max_pos, float* xnext,
                              hipStream_t st, int host_s1 = 0);
+// The decoder-fault decode's small kernels (csrc/qtx_decode.hip).  rec_ids int64 / rec_logp
+// float [B][2][2]: [b][0] the golden, [b][1] the faulty top 2 of the corrupted step.
+//   gold: rec[b][0] = entry (b, step) of top_ids / top_logp [B][top_bs][2]
+//   tail: rec[b][1] -> ids[b][step + 1] (row stride ids_bs), entry (b, step) of top_ids /
+//         top_logp [B][ids_bs - 1][2], changed[b] = golden winner != faulty winner (each
+//         destination may be null); step + 1 < ids_bs
+//   causal_mask: mask [T][T] = (j <= i);  set_steps: position counters = value, arrival
+//   counters = 0, of step [4] and gsteps [G][4]
+hipError_t launch_dfault_gold(const int64_t* top_ids, const float* top_logp, long top_bs,
+                              int step, int B, int64_t* rec_ids, float* rec_logp, hipStream_t st);
+hipError_t launch_dfault_tail(const int64_t* rec_ids, const float* rec_logp, int B, int step,
+                              long ids_bs, int64_t* ids, int64_t* top_ids, float* top_logp,
+                              int* changed, hipStream_t st);
+hipError_t launch_causal_mask(uint8_t* mask, int T, hipStream_t st);
+hipError_t launch_set_steps(int* step, int* gsteps, int G, int value, hipStream_t st);
 hipError_t launch_rows(const RowArgs& a, hipStream_t st);
 hipError_t launch_attention(const AttnArgs& a, hipStream_t st);
 hipError_t launch_embed(const int64_t* ids, long ids_bs, int B, int T, const int* pos_dev,

@@ -6,6 +6,7 @@ Public surface mirrors the reference's entry points:
   run_module(module, feeds, ...)               ~ onnx_optimized_inference.run_module
   greedy_decode(model, src, src_mask, max_len, start_symbol)
   greedy_decode(..., return_scores=True) -> (ys, Scores)   ~ the campaign's torch.topk(prob, 2)
+  decode_fault_sweep(model, src, src_mask, max_len, start_symbol, trials)   ~ a campaign's trials
 """
 from .weights import (BOS, DEFAULT_SEED, EOS, PAD, UNK, ModelConfig, load_checkpoint,
                       positional_table, synthetic_state_dict, tensor_order)
@@ -13,7 +14,8 @@ from .weights import (BOS, DEFAULT_SEED, EOS, PAD, UNK, ModelConfig, load_checkp
 __all__ = ["BOS", "EOS", "PAD", "UNK", "DEFAULT_SEED", "ModelConfig", "load_checkpoint",
            "positional_table", "synthetic_state_dict", "tensor_order", "QtxModel",
            "InferenceSession", "run_module", "set_default_model", "greedy_decode",
-           "greedy_decode_fault", "Scores", "FaultStepRecord", "make_src_mask", "lib"]
+           "greedy_decode_fault", "decode_fault_sweep", "plan_sweep", "SweepStats", "Scores",
+           "FaultStepRecord", "make_src_mask", "lib"]
 
 
 def __getattr__(name):
@@ -24,8 +26,8 @@ def __getattr__(name):
     if name in ("InferenceSession", "run_module", "set_default_model"):
         from . import session
         return getattr(session, name)
-    if name in ("greedy_decode", "greedy_decode_fault", "Scores", "FaultStepRecord",
-                "make_src_mask"):
+    if name in ("greedy_decode", "greedy_decode_fault", "decode_fault_sweep", "plan_sweep",
+                "SweepStats", "Scores", "FaultStepRecord", "make_src_mask"):
         from . import decode
         return getattr(decode, name)
     if name == "lib":

@@ -98,6 +98,11 @@ SIGNATURES = {
     "qtx_decode_argmax_embed": (I32, [P, P, I32, P, I64, P, P, P]),
     "qtx_greedy_scored_workspace_size": (SZ, [P, I32, I32, I32]),
     "qtx_greedy_decode_scored": (I32, [P, P, P, I32, I32, I32, I64, P, P, P, P, SZ, FP, P]),
+    "qtx_greedy_dfault_workspace_size": (SZ, [P, I32, I32, I32]),
+    "qtx_greedy_decode_dfault": (I32, [P, P, P, I32, I32, I32, I64, P, P, P, P, P, P, SZ, FP,
+                                       I32, P]),
+    "qtx_greedy_dfault_resume": (I32, [P, I32, I32, I32, P, P, P, P, P, P, SZ, FP, I32,
+                                       C.POINTER(I32), P]),
     "qtx_generator_top2": (I32, [P, P, I32, P, P, P, SZ, P]),
     "qtx_decode_top2_embed": (I32, [P, P, I32, P, I64, P, P, P, P, P]),
     "qtx_decode_generator": (I32, [P, P, I32, P, P, P]),

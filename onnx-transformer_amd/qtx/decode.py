@@ -70,7 +70,7 @@ def greedy_decode(model: QtxModel, src, src_mask, max_len: int, start_symbol: in
 
 def greedy_decode_fault(model: QtxModel, src, src_mask, max_len: int, start_symbol: int = 0,
                         fault=None, target_inference_number: int = 1,
-                        return_scores: bool = False):
+                        return_scores: bool = False, kv_cache: bool = False):
     """Greedy decode with one injected fault, the reference campaign's loop
     (parallelized_inject_onnx_transformer.py:536-720): an encoder fault corrupts the single
     encoder run (memory); a decoder fault corrupts only the decoder run of step
@@ -81,7 +81,10 @@ def greedy_decode_fault(model: QtxModel, src, src_mask, max_len: int, start_symb
     decode.  Decoder fault: every step's top 2 of the faulty decode, and in
     ``Scores.fault_step`` the campaign's record of the corrupted step (:711-740): the top 2
     of one extra fault-free decoder run on the same prefix (the reference's ``out_2``) and of
-    the faulty run, and token_changed per sentence."""
+    the faulty run, and token_changed per sentence.
+    kv_cache=True: a decoder fault runs as ONE KV-cached library call
+    (qtx_greedy_decode_dfault: cached golden steps up to the corrupted one, one faulty
+    full-prefix pass for its token, cached steps after it) with the same results, bit for bit."""
     import torch
     src = np.ascontiguousarray(np.asarray(src), np.int64)
     B, S = src.shape
@@ -97,6 +100,9 @@ def greedy_decode_fault(model: QtxModel, src, src_mask, max_len: int, start_symb
         if return_scores:
             return out[0].cpu().numpy(), Scores(out[1].cpu().numpy(), out[2].cpu().numpy())
         return out.cpu().numpy()
+    if kv_cache:
+        return _decode_dfault_cached(model, srcd, md, max_len, start_symbol, dec_fault,
+                                     target_inference_number, return_scores)
     memory = model.encode(model.embed(srcd, "src"), md)
     model.check()                               # the encode's device errors, before the loop
     ys = torch.full((B, 1), int(start_symbol), dtype=torch.int64, device=dev)
@@ -124,6 +130,92 @@ def greedy_decode_fault(model: QtxModel, src, src_mask, max_len: int, start_symb
     top_ids = torch.stack([t[0] for t in tops], dim=1) if tops else torch.empty((B, 0, 2), dtype=torch.int64)
     top_logp = torch.stack([t[1] for t in tops], dim=1) if tops else torch.empty((B, 0, 2))
     return ys.cpu().numpy(), Scores(top_ids.cpu().numpy(), top_logp.cpu().numpy(), record)
+
+
+def _fault_step(target_inference_number: int, max_len: int) -> int:
+    """The step a campaign's target_inference_number corrupts; max_len - 1 (a step that does
+    not exist: the fault is never applied) when the loop never reaches that number."""
+    step = int(target_inference_number) - 1
+    return step if 0 <= step < max_len - 1 else max_len - 1
+
+
+def _record(step, rec_ids, rec_logp):
+    ri, rl = rec_ids.cpu().numpy(), rec_logp.cpu().numpy()
+    return FaultStepRecord(step, ri[:, 0].copy(), rl[:, 0].copy(), ri[:, 1].copy(), rl[:, 1].copy())
+
+
+def _decode_dfault_cached(model, srcd, md, max_len, start_symbol, fault, target_inference_number,
+                          return_scores):
+    step = _fault_step(target_inference_number, max_len)
+    out = model.greedy_dfault(srcd, md, fault, step, max_len=max_len, start=start_symbol,
+                              scores=return_scores)
+    model.check()
+    if not return_scores:
+        return out.cpu().numpy()
+    ys, top_ids, top_logp, rec_ids, rec_logp = out
+    record = _record(step, rec_ids, rec_logp) if step < max_len - 1 else None
+    return ys.cpu().numpy(), Scores(top_ids.cpu().numpy(), top_logp.cpu().numpy(), record)
+
+
+@dataclasses.dataclass
+class SweepStats:
+    """decode_fault_sweep's counts: trials in all; ``n_resumed`` whose fault changed a token,
+    so the steps after it ran again; ``n_skipped`` whose fault was masked, so nothing ran
+    after the faulty pass; ``n_never`` whose step the decode never reaches (golden)."""
+    n_trials: int = 0
+    n_resumed: int = 0
+    n_skipped: int = 0
+    n_never: int = 0
+
+
+def plan_sweep(steps) -> list:
+    """The order in which a sweep visits its trials: a permutation of range(len(steps)),
+    descending in step and stable for equal steps.  A resumed trial rewrites the KV cache
+    above its own step only, so in this order every trial finds its prefix golden."""
+    return sorted(range(len(steps)), key=lambda k: -int(steps[k]))
+
+
+def decode_fault_sweep(model: QtxModel, src, src_mask, max_len: int, start_symbol: int, trials):
+    """A campaign's trials on one batch of sentences: ``trials`` = [(Fault, target_inference_number),
+    ...], decoder faults only (ValueError otherwise).  One scored golden KV-cached decode, then
+    one resume per trial in plan_sweep's order (qtx_greedy_dfault_resume): the faulty pass, and
+    the steps after it only when a token changed.  Returns (results, SweepStats): results in the
+    caller's order, each (ys, Scores) with Scores.fault_step set, numpy, equal to
+    greedy_decode_fault(..., fault, target_inference_number, return_scores=True)."""
+    import torch
+    trials = list(trials)
+    for f, _ in trials:
+        if f is None or f.module != 1:
+            raise ValueError("decode_fault_sweep takes decoder faults (module 1)")
+    stats = SweepStats(n_trials=len(trials))
+    if not trials:
+        return [], stats
+    src = np.ascontiguousarray(np.asarray(src), np.int64)
+    B, S = src.shape
+    srcd = torch.from_numpy(src).to(model.device)
+    md = to_u8_mask(src_mask, model.device).reshape(B, S)
+    steps = [_fault_step(tin, max_len) for _, tin in trials]
+    ws = model.dfault_workspace(B, S, max_len)
+    gold = model.greedy_dfault(srcd, md, trials[0][0], max_len - 1, max_len=max_len,
+                               start=start_symbol, scores=True, ws=ws)
+    model.check()
+    g_ys, g_ids, g_logp = (t.cpu().numpy() for t in gold[:3])
+    results = [None] * len(trials)
+    for k in plan_sweep(steps):
+        if steps[k] >= max_len - 1:
+            stats.n_never += 1
+            results[k] = (g_ys.copy(), Scores(g_ids.copy(), g_logp.copy(), None))
+            continue
+        ys, top_ids, top_logp, rec_ids, rec_logp, changed = model.greedy_dfault_resume(
+            ws, B, S, trials[k][0], steps[k], max_len=max_len)
+        if changed.any():
+            stats.n_resumed += 1
+        else:
+            stats.n_skipped += 1
+        results[k] = (ys.cpu().numpy(), Scores(top_ids.cpu().numpy(), top_logp.cpu().numpy(),
+                                               _record(steps[k], rec_ids, rec_logp)))
+    model.check()
+    return results, stats
 
 
 def make_src_mask(src, pad: int = PAD):

@@ -180,6 +180,59 @@ class QtxModel:
         return ids
 
     @_on_device
+    def dfault_workspace(self, B: int, S: int, max_len: int):
+        """A workspace of its own for greedy_dfault / greedy_dfault_resume (uint8 device
+        tensor): a resume reads what the last call left in it, so it is not the shared
+        per-thread scratch of the other entry points."""
+        torch = _torch()
+        nb = _lib.lib().qtx_greedy_dfault_workspace_size(self.handle, B, S, max_len)
+        return torch.empty(max(int(nb), 256), dtype=torch.uint8, device=self.device)
+
+    def _dfault_outputs(self, B, max_len, scores):
+        torch = _torch()
+        ids = torch.empty((B, max_len), dtype=torch.int64, device=self.device)
+        if not scores:
+            return ids, None, None, None, None
+        top_ids = torch.empty((B, max_len - 1, 2), dtype=torch.int64, device=self.device)
+        top_logp = torch.empty((B, max_len - 1, 2), dtype=torch.float32, device=self.device)
+        rec_ids = torch.empty((B, 2, 2), dtype=torch.int64, device=self.device)
+        rec_logp = torch.empty((B, 2, 2), dtype=torch.float32, device=self.device)
+        return ids, top_ids, top_logp, rec_ids, rec_logp
+
+    @_on_device
+    def greedy_dfault(self, src, src_mask_u8, fault, fault_step: int, max_len: int = 72,
+                      start: int = 0, scores: bool = False, ws=None):
+        """KV-cached greedy decode with one decoder fault at step ``fault_step``
+        (qtx_greedy_decode_dfault).  src int64 [B,S], src_mask [B,S] u8 -> ids int64
+        [B,max_len]; scores=True: (ids, top_ids, top_logp, rec_ids, rec_logp), the record
+        [B,2,2] ([:,0] golden, [:,1] faulty top 2) meaningful when fault_step < max_len-1.
+        ws: a dfault_workspace to resume on later (default: the thread's scratch)."""
+        B, S = src.shape
+        ids, top_ids, top_logp, rec_ids, rec_logp = self._dfault_outputs(B, max_len, scores)
+        if ws is None:
+            ws = self.workspace(_lib.lib().qtx_greedy_dfault_workspace_size(self.handle, B, S, max_len))
+        _lib.call("qtx_greedy_decode_dfault", self.handle, _ptr(src), _ptr(src_mask_u8), B, S,
+                  max_len, int(start), _ptr(ids), _ptr(top_ids), _ptr(top_logp), _ptr(rec_ids),
+                  _ptr(rec_logp), _ptr(ws), ws.numel(),
+                  C.byref(fault.to_c()) if fault is not None else None, int(fault_step),
+                  _stream(self.device))
+        return (ids, top_ids, top_logp, rec_ids, rec_logp) if scores else ids
+
+    @_on_device
+    def greedy_dfault_resume(self, ws, B: int, S: int, fault, fault_step: int, max_len: int = 72):
+        """One more decoder-fault trial on the workspace a scored greedy_dfault (or a resume)
+        left, for the same sentences (qtx_greedy_dfault_resume) -> (ids, top_ids, top_logp,
+        rec_ids, rec_logp, changed): changed, a host int32 array [B], says whose token the
+        fault changed.  Synchronises the stream."""
+        ids, top_ids, top_logp, rec_ids, rec_logp = self._dfault_outputs(B, max_len, True)
+        changed = (C.c_int32 * B)()
+        _lib.call("qtx_greedy_dfault_resume", self.handle, B, S, max_len, _ptr(ids), _ptr(top_ids),
+                  _ptr(top_logp), _ptr(rec_ids), _ptr(rec_logp), _ptr(ws), ws.numel(),
+                  C.byref(fault.to_c()) if fault is not None else None, int(fault_step), changed,
+                  _stream(self.device))
+        return ids, top_ids, top_logp, rec_ids, rec_logp, np.array(changed[:], np.int32)
+
+    @_on_device
     def embed(self, ids, which: str = "src", pos0: int = 0):
         torch = _torch()
         B, T = ids.shape
