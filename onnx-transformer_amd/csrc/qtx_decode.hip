@@ -770,16 +770,18 @@ hipError_t launch_skinny(const SkinnyArgs& g, int wbits, hipStream_t st) {
 // 2-6 KB of reads), attends over its head and writes its 64 fp32 context values plus
 // their absmax; the per-token quantization of the context row happens in the prologue of
 // the output-projection GEMM (A_F32Q), so no cross-workgroup step is needed here.
-// Keys staged in LDS (<= 128).  Grid (B, 8): the 8 heads of sentence b share blockIdx.x,
+// At most 128 keys.  The scores run on the int8 MFMA (round 9): the head dimension, 64, is one
+// K-step of v_mfma_i32_16x16x64_i8, and its B operand for 16 keys is one uint4 per lane (key
+// 16 i + lane % 16, byte chunk lane / 16), so the key rows are loaded straight into fragment
+// layout and never staged in LDS; the A operand repeats the q codes in all 16 rows.
+// Grid (B, 8): the 8 heads of sentence b share blockIdx.x,
 // so with B % 8 == 0 they land on one XCD (workgroups go round-robin over the 8 XCDs).
 // The value cache is kept in groups of 4 keys (round 6): byte ((b * G4 + j / 4) * 512 + d) * 4
 // + j % 4 holds v[b][j][d] (G4 = ceil(kv_bs / 4)), so one dword is 4 consecutive keys of one
 // dim — the PV's 4-key step in one ds_read_b32 and 4 SDWA conversions instead of 4 byte
-// reads.  Key rows are staged 20 dwords apart (16 B aligned: ds_read_b128 / ds_write_b128,
-// conflict-free: 20 j mod 64 steps through distinct 4-bank groups over 16 lanes).
+// reads.
 // =====================================================================================
 constexpr int DEC_MAXK = 128;
-constexpr int DEC_KST = 20;   // staged key row stride in dwords
 
 // The lead blocks of k_dec_attn (kernel-argument preload, above): what the loads of phase 0
 // need.  Self: the device position counter (read only by a step replayed at several
@@ -816,20 +818,23 @@ __device__ __forceinline__ DecAttnArgs da_args(const KaLead& k, const DaTail& t)
 template <bool KV_NEW, int NIT>
 __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
   const DecAttnArgs a = da_args<KV_NEW>(QTX_KA_VALS, kt);
-  __shared__ __attribute__((aligned(16))) uint32_t Ks[DEC_MAXK * DEC_KST];   // key rows of this head
   // values of this head, 4-key groups: dword g * 64 + d = keys 4g .. 4g + 3 of dim d
   __shared__ __attribute__((aligned(16))) uint8_t Vs[DEC_MAXK * 64];
-  __shared__ float svs[DEC_MAXK];
   __shared__ __attribute__((aligned(16))) float PS[DEC_MAXK];   // RN(P_j * s_v[j]), 0 past Sk
-  __shared__ __attribute__((aligned(16))) int8_t qs[64];
+  // this step's q codes and (self) k codes of the head: 64 B each, read back as MFMA fragments
+  __shared__ __attribute__((aligned(16))) int8_t qs[KV_NEW ? 128 : 64];
   const int b = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
+  const int fr = lane & 15, fg = lane >> 4;    // MFMA fragment: column (key) fr, byte chunk fg
   QTX_STAMP(0);
   const float* yr = a.y + (long)b * a.ldy;
 
   // phase 0: every global load first (one memory latency): this step's q (k, v) rows
   // first — vmcnt retires in issue order, so their quantization (phase 1) then runs while
   // the cached keys and values are in flight — then the key/value rows of this head (row r
-  // = 4 uint4; lane takes row 16*i + lane/4, chunk lane%4; clamped: no divergent loads)
+  // = 4 uint4; lane takes row 16*i + lane%16, chunk lane/16 — the B fragment of the int8
+  // 16x16x64 MFMA for keys 16i .. 16i + 15, so the keys are never staged; the same 16 rows x
+  // 64 B per load instruction as any other lane <-> (row, chunk) map; clamped: no divergent
+  // loads)
   float4 yq[2], yk[2], yv[2];
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
@@ -849,7 +854,6 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
   const int nrows = KV_NEW ? (a.host_step1 > 0 ? a.host_step1 : (int)a.kv_bs) : a.S;
   const long kvb = (long)b * a.kv_bs;
   const long vgb = (long)b * ((a.kv_bs + 3) >> 2);     // the sentence's first value group
-  const int rsub = lane >> 2, ch = lane & 3;
   // values: per 16 keys, 4 groups x this head's 64 dims x 4 B = 1 KB, lane = group
   // 4 i + lane / 16, dims 4 (lane % 16) .. + 3
   const int vg = lane >> 4, vd = 4 * (lane & 15), glast = (nrows - 1) >> 2;
@@ -860,7 +864,7 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
   uint4 kr[NIT], vr[NIT];
 #pragma unroll
   for (int i = 0; i < NIT; ++i) {
-    const unsigned koff = (unsigned)(min(16 * i + rsub, nrows - 1) * 512 + 16 * ch);
+    const unsigned koff = (unsigned)(min(16 * i + fr, nrows - 1) * 512 + 16 * fg);
     const unsigned voff = (unsigned)(min(4 * i + vg, glast) * 2048 + 4 * vd);
     // non-temporal: each K/V row is read once per step by one wave, so it should not push
     // the weights (re-read every step) out of the XCD's L2 (B = 256: 36.2 -> 35.1 ms; the
@@ -872,7 +876,7 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
   const float* const skb = a.skc + kvb;
   const float* const svb = a.svc + kvb;
   float sk0 = skb[(unsigned)j0], sk1 = skb[(unsigned)j1];
-  const float sv0 = svb[(unsigned)j0], sv1 = svb[(unsigned)j1];
+  float sv0 = svb[(unsigned)j0], sv1 = svb[(unsigned)j1];
   bool keep0 = true, keep1 = true;
   if constexpr (!KV_NEW) {
     const uint8_t* const mb = a.mask + (long)b * a.S;
@@ -889,7 +893,7 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
   int Sk = KV_NEW ? step + 1 : a.S;
   if constexpr (!KV_NEW) {
     const int last = wave_max_i32(max(keep0 && lane < a.S ? lane + 1 : 0,
-                                      keep1 && lane + 64 < a.S ? lane + 65 : 0));
+                                      NIT > 4 && keep1 && lane + 64 < a.S ? lane + 65 : 0));
     if (last > 0) Sk = last;
   }
 
@@ -914,68 +918,77 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
     a.kc[row * 512 + h * 64 + lane] = kq;     // cache append (attention.py: k/v of this step)
     a.vc[((vgb + (step >> 2)) * 512 + h * 64 + lane) * 4 + (step & 3)] = vq;
     if (h == 0 && lane == 0) { a.skc[row] = sk; a.svc[row] = sv; }
+    qs[64 + lane] = kq;
+    if (lane == step) { sk0 = sk; sv0 = sv; }            // the key and value scales stay in the
+    if (lane + 64 == step) { sk1 = sk; sv1 = sv; }       // lane that scores the key (lane + 64 u)
   }
 
-  // phase 2: staged rows into LDS, then (self) the new row over the stale one
-#pragma unroll
-  for (int i = 0; i < NIT; ++i) {
-    const int r = min(16 * i + rsub, nrows - 1);
-    *reinterpret_cast<uint4*>(&Ks[r * DEC_KST + 4 * ch]) = kr[i];
-    *reinterpret_cast<uint4*>(Vs + (min(4 * i + vg, glast) * 64 + vd) * 4) = vr[i];
-  }
-  svs[j0] = sv0; svs[j1] = sv1;
+  // phase 2: the operand fragments.  A: the q codes' chunk fg in every row, so each of the 16
+  // rows of C holds the scores.  B: kr[i] as loaded; (self) this step's k codes replace the
+  // stale row `step` in the lanes that hold it (fragment step / 16, wave-uniform; column
+  // step % 16)
   __syncthreads();
+  const v4i qf = *reinterpret_cast<const v4i*>(qs + 16 * fg);
   if constexpr (KV_NEW) {
-    reinterpret_cast<int8_t*>(&Ks[step * DEC_KST])[lane] = kq;
-    Vs[((step >> 2) * 64 + lane) * 4 + (step & 3)] = (uint8_t)vq;
-    if (lane == 0) svs[step] = sv;
-    if (lane == step) sk0 = sk;            // the key scales stay in the lane that scores
-    if (lane + 64 == step) sk1 = sk;       // the key (lane + 64 u)
-    __syncthreads();
+    const uint4 kn = *reinterpret_cast<const uint4*>(qs + 64 + 16 * fg);
+    const bool own = fr == (step & 15);
+#pragma unroll
+    for (int i = 0; i < NIT; ++i)
+      if (i == (step >> 4) && own) kr[i] = kn;
   }
   QTX_STAMP(1);
 
-  // phase 3: scores (lane owns keys lane, lane+64), softmax, P quantization
-  uint32_t qd[16];
+  // phase 3: scores (lane owns keys lane, lane+64), softmax, P quantization.  One MFMA per 16
+  // keys, independent accumulators; int32 dot products, exact in any order
+  v4i sacc[NIT];
 #pragma unroll
-  for (int w = 0; w < 16; ++w) qd[w] = reinterpret_cast<const uint32_t*>(qs)[w];
-  // (the scores and exponentials stay in registers: lane owns keys lane, lane + 64)
-  float sc[2] = {0.0f, 0.0f};
+  for (int i = 0; i < NIT; ++i)
+    sacc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(qf, __builtin_bit_cast(v4i, kr[i]), v4i{0, 0, 0, 0}, 0, 0, 0);
+  // the values of this head into LDS while the MFMAs run, then (self) the new value row
+  // over the stale one: one wave, whose LDS writes land in program order; the barrier after
+  // the PS writes orders both before the PV phase's reads
+#pragma unroll
+  for (int i = 0; i < NIT; ++i)
+    *reinterpret_cast<uint4*>(Vs + (min(4 * i + vg, glast) * 64 + vd) * 4) = vr[i];
+  if constexpr (KV_NEW) {
+    Vs[((step >> 2) * 64 + lane) * 4 + (step & 3)] = (uint8_t)vq;
+  }
+  // key 16 i + fr is column fr of sacc[i] (C: column lane % 16, all rows equal): lane's key
+  // lane is in sacc[fg], key lane + 64 in sacc[4 + fg]
+  constexpr int NU = NIT > 4 ? 2 : 1;     // up to 64 rows: no second key slot
+  int dot[NU];
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    dot[u] = sacc[4 * u][0];
+#pragma unroll
+    for (int t = 1; t < 4; ++t)
+      if (4 * u + t < NIT) dot[u] = fg == t ? sacc[4 * u + t][0] : dot[u];
+  }
+  // (the scores and exponentials stay in registers: lane owns keys lane, lane + 64).  Both
+  // key slots go through the same straight-line arithmetic and a lane without a key (j >=
+  // Sk) drops its value by a select, so the two slots' chains interleave instead of running
+  // one after the other under two exec masks; what such a lane computes (from a stale
+  // scale, say) never reaches a sum: max and sum take it through the select alone, and
+  // x + 0.0f == x for the x >= 0 summed here
+  float sc[NU];
+  bool live[NU];
   float lmax = -3.0e38f;
 #pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int j = lane + 64 * u;
-    if (j < Sk) {
-      // the key row in 4 ds_read_b128; two partial int32 sums (exact in any order)
-      uint32_t kw[16];
-#pragma unroll
-      for (int w4 = 0; w4 < 4; ++w4) {
-        const uint4 t = *reinterpret_cast<const uint4*>(&Ks[j * DEC_KST + 4 * w4]);
-        kw[4 * w4] = t.x; kw[4 * w4 + 1] = t.y; kw[4 * w4 + 2] = t.z; kw[4 * w4 + 3] = t.w;
-      }
-      int a0 = 0, a1 = 0;
-#pragma unroll
-      for (int w = 0; w < 16; w += 2) {
-        a0 = __builtin_amdgcn_sdot4(qd[w], kw[w], a0, false);
-        a1 = __builtin_amdgcn_sdot4(qd[w + 1], kw[w + 1], a1, false);
-      }
-      const int acc = a0 + a1;
-      float s = (((float)acc * sq) * (u ? sk1 : sk0)) * 0.125f;
-      if (!(u ? keep1 : keep0)) s = -1.0e9f;
-      sc[u] = s;
-      lmax = fmaxf(lmax, s);
-    }
+  for (int u = 0; u < NU; ++u) {
+    live[u] = lane + 64 * u < Sk;
+    const int acc = dot[u];
+    float s = (((float)acc * sq) * (u ? sk1 : sk0)) * 0.125f;
+    if (!(u ? keep1 : keep0)) s = -1.0e9f;
+    sc[u] = s;
+    lmax = live[u] ? fmaxf(lmax, s) : lmax;
   }
   const float m = wave_max(lmax);
   float lsum = 0.0f;
 #pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int j = lane + 64 * u;
-    if (j < Sk) {
-      const float e = qexp(sc[u] - m);
-      sc[u] = e;
-      lsum = lsum + e;
-    }
+  for (int u = 0; u < NU; ++u) {
+    const float e = qexp(sc[u] - m);
+    sc[u] = e;
+    lsum = lsum + (live[u] ? e : 0.0f);
   }
   // P = rint((e / den) * 127) / 127: e / den by div_cr, unguarded (den in [1, Sk]: the
   // row max contributes qexp(0) == 1; e >= 2^-60 gives the correctly rounded quotient and
@@ -986,10 +999,10 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
   const float rden = 1.0f / den;
   const int nk16 = (Sk + 15) & ~15;
 #pragma unroll
-  for (int u = 0; u < 2; ++u) {
+  for (int u = 0; u < NU; ++u) {
     const int j = lane + 64 * u;
-    if (j < Sk) PS[j] = div127(rintf(div_cr(sc[u], den, rden) * 127.0f)) * svs[j];
-    else if (j < nk16) PS[j] = 0.0f;
+    const float ps = div127(rintf(div_cr(sc[u], den, rden) * 127.0f)) * (u ? sv1 : sv0);
+    if (j < nk16) PS[j] = live[u] ? ps : 0.0f;
   }
   __syncthreads();
   QTX_STAMP(2);
