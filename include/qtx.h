@@ -307,6 +307,57 @@ int32_t qtx_greedy_dfault_resume(const qtx_model* m, int32_t B, int32_t S, int32
                                  const qtx_fault* fault, int32_t fault_step,
                                  int32_t* changed_host, void* stream);
 
+/* ---- beam search with EOS stop ----
+ * The reference has no beam search (its only decode is the fixed-length greedy loop above):
+ * this entry cites generator.py:15 for the log-probabilities and nothing else.  The contract is
+ * tests/beam_ref.py, a beam search over the oracle's KV-cached DecodeState; results are equal
+ * bit for bit.
+ * Rows are r = b * K + k with K = beam.  Per row: score (float32), a finished flag, length,
+ * history [max_len] ([0] = start, every other entry starts as pad).
+ * Start: score 0 for k = 0 and -inf for k > 0; no row finished; input token = start.
+ * Step t = 0 .. max_len-2:
+ *   1. one KV-cached decoder step at position t on all B * K rows; cross K/V and the source
+ *      mask of row r are those of sentence r / K.
+ *   2. logp = the canonical log-softmax of the row's logits (the scored decode's, above: qlog,
+ *      not the platform logf).
+ *   3. candidates of sentence b: a live row k gives V candidates (fl32(score[k] + logp[k][v]),
+ *      flat = k * V + v), a value that is not finite (NaN, +-inf) taken as -inf; a finished row
+ *      gives exactly one candidate (score[k], flat = k * V + pad): its score does not change.
+ *   4. the K best under the total order "larger value, then smaller flat"; new slot j takes the
+ *      j-th best: parent = flat / V, token = flat % V, score = value.  The order is total, so
+ *      the result does not depend on the order of the reduction.
+ *   5. history, length, finished flag and every layer's self K/V cache rows (codes and scales,
+ *      positions 0 .. t) of slot j become those of its parent; history[t+1] = token; finished =
+ *      parent finished or token == eos; length = t + 1 unless the parent was finished.
+ *   6. stop when every row is finished, or after step max_len - 2.  (A step after the stop
+ *      changes nothing: a finished row only re-selects itself with pad.)
+ * Outputs: hyp_ids int64 [B, K, max_len]; hyp_score float [B, K], the raw cumulative
+ * log-probability, in search order (best first); hyp_len int32 [B, K], tokens after the start
+ * symbol including the EOS; steps_run (HOST pointer, may be NULL): decoder steps launched.
+ * No length normalisation here (qtx/decode.py ranks).
+ * The encoder and the cross K/V GEMM run once on the B sentences.  The step is the greedy
+ * decode's on B * K rows — the fused step where the greedy decode would take it, else the
+ * unfused one, so every config qtx_model_create accepts beam-decodes — with the tail replaced
+ * by k_beam_select and k_beam_reorder (csrc/qtx_decode.hip; the caches are permuted in place).
+ * Steps run in chunks of QTX_GRAPH_STEPS (default 8): the fused step as captured graphs of
+ * that many steps and of one step (graphs of their own; QTX_NO_GRAPH and the unfused step run
+ * eager); one group (QTX_DECODE_GROUPS is ignored).  early_exit != 0: after each chunk but the
+ * last the count of live rows is copied to the host (one 4-byte synchronising copy) and the
+ * decode stops at zero, so steps_run is the stop step rounded up to the chunk; early_exit == 0:
+ * asynchronous, every step runs.  The outputs are the same either way.
+ * Refused before anything is launched: beam outside 1 .. 8 or above tgt_vocab, start / eos /
+ * pad outside the vocabulary, eos == pad, max_len above the positional table: QTX_E_INVALID;
+ * B * beam * tgt_vocab or B * beam * max_len * d_model >= 2^30, tgt_vocab or B * beam >= 2^21
+ * (the select's 32-bit embedding offsets): QTX_E_UNSUPPORTED; a short
+ * workspace: QTX_E_WORKSPACE.  ws: qtx_beam_workspace_size bytes. */
+size_t qtx_beam_workspace_size(const qtx_model* m, int32_t B, int32_t S, int32_t max_len,
+                               int32_t beam);
+int32_t qtx_beam_decode(const qtx_model* m, const int64_t* src, const uint8_t* src_mask,
+                        int32_t B, int32_t S, int32_t max_len, int32_t beam, int64_t start,
+                        int64_t eos, int64_t pad, int32_t early_exit, int64_t* hyp_ids,
+                        float* hyp_score, int32_t* hyp_len, int32_t* steps_run, void* ws,
+                        size_t ws_bytes, void* stream);
+
 /* Embeddings + positional encoding: which = 0 (src) / 1 (tgt); ids int64 [B,T] ->
  * out [B,T,d], positions pos0 .. pos0+T-1. */
 int32_t qtx_embed(const qtx_model* m, int32_t which, const int64_t* ids, int32_t B, int32_t T,
@@ -524,6 +575,31 @@ int32_t qtx_decode_argmax_embed(const qtx_model* m, const float* logits, int32_t
 int32_t qtx_decode_top2_embed(const qtx_model* m, const float* logits, int32_t M, int64_t* ids,
                               int64_t ids_bs, int64_t* top_ids, float* top_logp,
                               int32_t* step_dev, float* x_next, void* stream);
+
+/* The beam step's tail, part 1 (beam search above, rules 2-5 without the caches): logits
+ * [B * beam, tgt_vocab] of the step at position s = step_dev[0].  Rewrites score float / fin /
+ * len int32 [B * beam] in place; writes parent [B * beam] (each slot's parent slot, 0 ..
+ * beam-1), the back-pointers bp_par / bp_tok int32 [max_len-1][B * beam] at row s (parent slot
+ * and token), the next decoder inputs x_next [B * beam, d_model] = tgt_embed(token) at
+ * position s + 1, and the four step words: step_dev[0] advanced by one, [1] and [2] (arrival
+ * counter and live accumulator: must be 0, left 0), [3] = the rows still live. */
+int32_t qtx_beam_select(const qtx_model* m, const float* logits, int32_t B, int32_t beam,
+                        int64_t eos, int64_t pad, int32_t max_len, int32_t* step_dev,
+                        float* score, int32_t* fin, int32_t* len, int32_t* parent,
+                        int32_t* bp_par, int32_t* bp_tok, float* x_next, void* stream);
+
+/* The beam step's tail, part 2: every layer's self K/V caches of slot j become those of slot
+ * parent[b * beam + j], in place (each byte offset of a sentence's beam regions is owned by one
+ * thread, which loads its beam chunks and then stores them by parent).  Per layer l and row r:
+ * kc + l * k_ls int8 [r][max_len][512]; vc + l * v_ls int8, v_grouped != 0: the fused step's
+ * 4-key groups [r][ceil(max_len/4)][512][4], else [r][max_len][512]; skc / svc + l * s_ls float
+ * [r][max_len] (k_ls, v_ls in bytes, multiples of 16; s_ls in floats).  Only the valid prefix
+ * moves: positions 0 .. n-1 with n = step_dev[0] clamped to max_len (grouped V: ceil(n / 4)
+ * groups); nothing else is written. */
+int32_t qtx_beam_reorder(int8_t* kc, int8_t* vc, float* skc, float* svc, int32_t B, int32_t beam,
+                         int32_t max_len, int32_t n_layers, int64_t k_ls, int64_t v_ls,
+                         int64_t s_ls, int32_t v_grouped, const int32_t* step_dev,
+                         const int32_t* parent, void* stream);
 
 /* The decode step's generator launch: logits [M, tgt_vocab] = generator(final LayerNorm(x)),
  * x fp32 [M, d_model] (decoder.py:16, generator.py:14).  rec (may be NULL): float

@@ -17,6 +17,7 @@
 #include "../../include/qtx.h"
 #include "qtx_kernels.h"
 #include "qtx_knobs.h"
+#include "qtx_carve.h"   // Arena, Scratch, CrossKV, GreedyWS, BeamWS and their carving
 
 using namespace qtx;
 
@@ -58,21 +59,8 @@ int fail(int code, const char* fmt, ...) {
                   __LINE__);                                                            \
   } while (0)
 
-inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 // a base the kernels' 16-byte vector loads / stores can take (null: not passed)
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// bump allocator over a caller-provided (or model-owned) device region
-struct Arena {
-  uint8_t* base = nullptr;
-  size_t cap = 0, used = 0;
-  template <class T>
-  T* take(size_t n) {
-    const size_t off = align_up(used);
-    used = off + n * sizeof(T);
-    return base ? reinterpret_cast<T*>(base + off) : nullptr;
-  }
-};
 
 }  // namespace
 
@@ -659,43 +647,7 @@ int32_t qtx_model_norm(const qtx_model* m, int32_t module, int32_t layer, int32_
 // =======================================================================================
 namespace {
 
-// scratch for one stack pass over M rows (fp32 residual stream + quant buffers)
-struct Scratch {
-  float* x;      // [M, D] residual stream
-  int8_t* a8;    // [M, max(D, F)] activation ints (max K)
-  float* sa;     // [M]
-  float* y;      // [M, max(3D, F)] GEMM output
-  int8_t* q8;    // [M, D]   q8, k8, v8 contiguous ([3][M][D]) with sq, sk, sv ([3][M]):
-  float* sq;     // [M]      the row GEMM writes the three quantized projections in one
-  int8_t* k8;    // [M, D]   launch (tile stride M*D / M)
-  float* sk;
-  int8_t* v8;    // [M, D]
-  float* sv;
-  float* ctx;    // [M, D]
-  int8_t* h8;    // [M, F]  quantized FFN hidden
-  float* sh;     // [M]
-  float* pmax;   // [F/512, M] FFN1 per-tile row maxima
-  unsigned* status = nullptr;   // the call's status word (call_status_begin)
-};
-
-Scratch carve_scratch(Arena& ar, const qtx_config& c, long M) {
-  const int D = c.d_model, F = c.d_ff;
-  const int Y = 3 * D > F ? 3 * D : F;
-  Scratch s;
-  s.x = ar.take<float>(M * D);
-  // the inputs of every linear, K = D or F wide (d_ff 256: D is the wider);
-  // + 1 row: KP row pairs of an odd M
-  s.a8 = ar.take<int8_t>((M + 1) * (D > F ? D : F));
-  s.sa = ar.take<float>(M);
-  s.y = ar.take<float>(M * Y);
-  s.q8 = ar.take<int8_t>(3 * M * D); s.k8 = s.q8 + M * D; s.v8 = s.k8 + M * D;
-  s.sq = ar.take<float>(3 * M); s.sk = s.sq + M; s.sv = s.sk + M;
-  s.ctx = ar.take<float>(M * D);
-  s.h8 = ar.take<int8_t>((M + 1) * F);
-  s.sh = ar.take<float>(M);
-  s.pmax = ar.take<float>((F / 512 + 1) * M);
-  return s;
-}
+// (Scratch / carve_scratch, the scratch for one stack pass over M rows: qtx_carve.h)
 
 // ---- building blocks ------------------------------------------------------------------
 RowArgs rows_quant(const float* x, long ldx, int rows, int D, int8_t* q, float* s) {
@@ -1153,33 +1105,7 @@ size_t enc_ws(const qtx_config& c, int B, int S) {
   return align_up(ar.used);
 }
 
-// decoder-specific scratch: quantized memory + cross K/V for all layers
-struct CrossKV {
-  int8_t* am8;  // [B*S, D] quantized memory (per token, layer independent)
-  float* sam;
-  std::vector<int8_t*> k8, v8;
-  std::vector<float*> sk, sv;
-  float* y;     // [B*S, 2D]
-};
-
-CrossKV carve_cross(Arena& ar, const qtx_config& c, long Ms) {
-  const int D = c.d_model;
-  CrossKV x;
-  x.am8 = ar.take<int8_t>(Ms * D);
-  x.sam = ar.take<float>(Ms);
-  x.y = ar.take<float>(Ms * 2 * D);
-  // k8 / v8 of every layer contiguous (tile t = 2 l + {0: K, 1: V} at t * Ms * D), and
-  // sk / sv likewise (t * Ms): the layout of one row GEMM's per-512-column-tile outputs
-  int8_t* kv = ar.take<int8_t>(2L * c.n_layers * Ms * D);
-  float* sc = ar.take<float>(2L * c.n_layers * Ms);
-  for (int l = 0; l < c.n_layers; ++l) {
-    x.k8.push_back(kv ? kv + 2L * l * Ms * D : nullptr);
-    x.v8.push_back(kv ? kv + (2L * l + 1) * Ms * D : nullptr);
-    x.sk.push_back(sc ? sc + 2L * l * Ms : nullptr);
-    x.sv.push_back(sc ? sc + (2L * l + 1) * Ms : nullptr);
-  }
-  return x;
-}
+// (CrossKV / carve_cross, quantized memory + cross K/V for all layers: qtx_carve.h)
 
 // memory -> per-layer cross K/V (get_quantized_model.py:160-168: K/V outputs quantized)
 int cross_kv(const qtx_model* m, const float* memory, int Ms, CrossKV& x, hipStream_t st,
@@ -1238,35 +1164,7 @@ size_t dec_ws(const qtx_config& c, int B, int T, int S) {
   return align_up(ar.used);
 }
 
-// greedy decode workspace: encoder scratch, decoder step scratch (M=B), cross K/V,
-// self K/V caches [L][B][max_len][D], memory, logits, step counter
-struct GreedyWS {
-  Scratch enc, dec;
-  CrossKV cross;
-  std::vector<int8_t*> cvg;   // the cross values in k_dec_attn's 4-key groups, per layer
-  std::vector<int8_t*> kc, vc;   // self K [B][max_len][D]; V in 4-key groups (fused step) or
-                                 // [B][max_len][D] (unfused step)
-  std::vector<float*> skc, svc;
-  float* memory;
-  float* xo;
-  float* logits;
-  float* rec;         // [B][ceil(V/16)][4] the generator's per-strip top-2 records (folded tail)
-  int* step;          // [0] = decode position, [1] = argmax arrival counter
-  float* pmax_a;      // [8][B]    per-head absmax of the attention context (A_F32Q input)
-  float* pmax_f;      // [F/16][B] per-column-tile absmax of FFN1's output
-  // fused-decode sub-batches: step scratch (grp[0] = dec) and step counters, 4 ints each
-  std::vector<Scratch> grp;
-  int* gsteps;
-  int64_t* ids;       // [B][max_len] the decode writes here; copied out to the caller's ids
-  uint8_t* mask;      // [B][S] staged copy of the caller's src_mask
-  // scored decode only (else null): [B][max_len-1][2] the two best ids / log-probs of every
-  // step; copied out to the caller's top_ids / top_logp
-  int64_t* top_ids = nullptr;
-  float* top_logp = nullptr;
-  // the decoder-fault decode (qtx_greedy_decode_dfault): its tail is never folded into the
-  // next step's first launch (a step may follow the faulty pass, not a generator launch)
-  bool no_fold = false;
-};
+// (GreedyWS, the greedy decode workspace, and BeamTail, the beam step's tail: qtx_carve.h)
 
 // Sub-batch split of the fused decode.  Sentences are independent (per-token quantization:
 // no value depends on another sentence), and one sub-batch's step is a chain of ~50
@@ -1369,6 +1267,19 @@ SkinnyArgs skinny(int wbits, const QLin& L, int M, int amode, int flags, float* 
   return s;
 }
 
+// The beam step's tail on the step's R = B * beam rows: the selection (scores, parents, tokens,
+// next inputs, position + 1, rows still live), then the caches of every layer by parent.
+int beam_tail(const qtx_model* m, GreedyWS& g, int R, int max_len, hipStream_t st) {
+  const qtx_config& c = m->cfg;
+  const BeamTail& b = *g.beam;
+  HIPCHK(launch_beam_select(g.logits, R / b.K, b.K, c.tgt_vocab, b.eos, b.pad, max_len, g.step,
+                            b.st.score, b.st.fin, b.st.len, b.st.parent, b.st.bp_par,
+                            b.st.bp_tok, m->tgt_lut, m->pe, c.max_len, g.dec.x, st));
+  HIPCHK(launch_beam_reorder(b.kc0, b.vc0, b.skc0, b.svc0, R / b.K, b.K, max_len, c.n_layers,
+                             b.k_ls, b.v_ls, b.s_ls, b.grouped ? 1 : 0, g.step, b.st.parent, st));
+  return QTX_OK;
+}
+
 // One KV-cached decoder step for every sentence, 8 kernels per layer + 2:
 //   [LN+QKV] [self-attn] [O+res] [LN+Qc] [cross-attn] [Oc+res] [LN+FFN1+relu] [FFN2+res]
 //   [final LN + generator] [log_softmax/argmax + next embedding + step++]
@@ -1401,7 +1312,7 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
   // embeds it and stores ids / x itself (launch_skinny_tok) — a step is then 49 launches.
   // Only the last step still ends with the argmax kernel.
   const bool fold = !knobs().no_tail_fold && host_pos && !g.top_ids && wb == 8 && fused_ln &&
-                    !knobs().ablate && !knobs().dbg_tail && !g.no_fold;
+                    !knobs().ablate && !knobs().dbg_tail && !g.no_fold && !g.beam;
   Scratch& s = g.dec;
   // Timing experiments only (wrong results): QTX_ABLATE=<bitmask> drops kernel classes
   // from the step (replaced by an empty kernel with QTX_ABLATE_NOP=1) to measure what
@@ -1503,6 +1414,7 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
   QTX_RUN(256, launch_generator_mfma(s.x, D, B, m->dec_norm[0], m->dec_norm[1], m->gen_wt,
                                      m->gen_b, c.tgt_vocab, g.logits, st, fold ? g.rec : nullptr));
   if (fold && t_host + 2 < max_len) return QTX_OK;   // the next step's first launch is the tail
+  if (g.beam) return beam_tail(m, g, B, max_len, st);
   if (g.top_ids)   // scored decode: the tail that also writes the step's two best (id, logp)
     QTX_RUN(256, launch_top2_embed(g.logits, B, c.tgt_vocab, ids, max_len, g.top_ids, g.top_logp,
                                    g.step, reinterpret_cast<unsigned*>(g.step + 1), m->tgt_lut,
@@ -1522,8 +1434,9 @@ int greedy_step_unfused(const qtx_model* m, GreedyWS& g, int B, int S, int max_l
   const qtx_config& c = m->cfg;
   const int D = c.d_model;
   Scratch& s = g.dec;
-  HIPCHK(launch_embed(ids, max_len, B, 1, g.step, 0, m->tgt_lut, c.tgt_vocab, m->pe,
-                      c.max_len, s.x, D, st));
+  if (!g.beam)   // (the beam step's input row comes from the previous step's select)
+    HIPCHK(launch_embed(ids, max_len, B, 1, g.step, 0, m->tgt_lut, c.tgt_vocab, m->pe,
+                        c.max_len, s.x, D, st));
   for (int l = 0; l < c.n_layers; ++l) {
     const DecLayer& L = m->dec[l];
     RC(ln_quant(s.x, B, L.ln[0], D, s.a8, s.sa, st));
@@ -1547,6 +1460,7 @@ int greedy_step_unfused(const qtx_model* m, GreedyWS& g, int B, int S, int max_l
   }
   RC(ln_out(s.x, B, m->dec_norm, D, g.xo, st));
   HIPCHK(launch_generator(g.xo, D, B, m->gen_w, m->gen_b, c.tgt_vocab, g.logits, st));
+  if (g.beam) return beam_tail(m, g, B, max_len, st);   // (it advances the position itself)
   if (g.top_ids)
     HIPCHK(launch_logsoftmax_top2(g.logits, B, c.tgt_vocab, ids, max_len, g.step, 1, g.top_ids,
                                   g.top_logp, max_len - 1, st));
@@ -2464,6 +2378,207 @@ int32_t qtx_greedy_dfault_resume(const qtx_model* m, int32_t B, int32_t S, int32
     HIPCHK(hipMemcpyAsync(rec_ids, w.rec_ids, (size_t)B * 4 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(rec_logp, w.rec_logp, (size_t)B * 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
+  return QTX_OK;
+}
+
+}  // extern "C"
+
+// =======================================================================================
+// Beam-search decode with EOS stop (include/qtx.h: qtx_beam_decode)
+// =======================================================================================
+namespace {
+
+// (BeamWS / carve_beam / beam_ws, the workspace: qtx_carve.h)
+
+// What precedes the steps: the encoder and the cross K/V GEMM once on the B sentences, their
+// results replicated to the B * K hypotheses, the search state and the first decoder input.
+int beam_prologue(const qtx_model* m, BeamWS& w, const int64_t* src, int B, int K, int S,
+                  int64_t start, bool fused, hipStream_t st) {
+  const qtx_config& c = m->cfg;
+  const long D = c.d_model, S4 = (S + 3) & ~3;
+  GreedyWS& g = w.g;
+  HIPCHK(launch_embed(src, S, B, S, nullptr, 0, m->src_lut, c.src_vocab, m->pe, c.max_len,
+                      g.enc.x, (long)S * D, st));
+  RC(encoder_run(m, g.enc.x, w.mask_b, B, S, g.memory, g.enc, st, nullptr));
+  RC(cross_kv(m, g.memory, B * S, w.cross_b, st));
+  if (fused) {
+    const long v_ls = c.n_layers > 1 ? (long)(w.cross_b.v8[1] - w.cross_b.v8[0]) : 0;
+    HIPCHK(launch_vgroup4(w.cross_b.v8[0], v_ls, c.n_layers, B, S, w.cvg_b, (long)B * S4 * D, st));
+  }
+  for (int l = 0; l < c.n_layers; ++l) {
+    HIPCHK(launch_beam_rep(w.cross_b.k8[l], g.cross.k8[l], B, K, S * D, st));
+    if (fused)
+      HIPCHK(launch_beam_rep(w.cvg_b + (size_t)l * B * S4 * D, g.cvg[l], B, K, S4 * D, st));
+    else
+      HIPCHK(launch_beam_rep(w.cross_b.v8[l], g.cross.v8[l], B, K, S * D, st));
+    HIPCHK(launch_beam_rep(w.cross_b.sk[l], g.cross.sk[l], B, K, S * 4L, st));
+    HIPCHK(launch_beam_rep(w.cross_b.sv[l], g.cross.sv[l], B, K, S * 4L, st));
+  }
+  HIPCHK(launch_beam_rep(w.mask_b, g.mask, B, K, S, st));
+  const BeamState& bs = w.tail.st;
+  HIPCHK(launch_beam_init(B, K, bs.score, bs.fin, bs.len, bs.parent, g.step, st));
+  HIPCHK(launch_fill_col(bs.ids0, 1, B * K, start, st));
+  HIPCHK(launch_embed(bs.ids0, 1, B * K, 1, nullptr, 0, m->tgt_lut, c.tgt_vocab, m->pe, c.max_len,
+                      g.dec.x, D, st));
+  return QTX_OK;
+}
+
+// n more beam steps at the device counter's position, with dfault_steps' path selection: the
+// unfused step or eager fused steps (QTX_NO_GRAPH), else captured graphs — one of `big` steps
+// when n == big, else n replays of the one-step graph.  One group: no sub-batches.
+int beam_steps(const qtx_model* m, BeamWS& w, int R, int S, int max_len, int n, int big,
+               bool fused, hipStream_t st) {
+  GreedyWS& g = w.g;
+  if (!fused || knobs().no_graph) {
+    for (int t = 0; t < n; ++t)
+      RC(fused ? greedy_step_fused(m, g, R, S, max_len, nullptr, g.mask, st, -1)
+               : greedy_step_unfused(m, g, R, S, max_len, nullptr, g.mask, st));
+    return QTX_OK;
+  }
+  qtx_model* mm = const_cast<qtx_model*>(m);
+  std::lock_guard<std::mutex> lock(mm->mu);
+  DeviceGuard dg(mm->device);
+  if (!mm->gstream[0]) {
+    HIPCHK(hipStreamCreateWithFlags(&mm->gstream[0], hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&mm->ev_out[0], hipEventDisableTiming));
+  }
+  const Knobs& kn = knobs();
+  const BeamTail& bt = w.tail;
+  // the beam step's own graphs: the select's eos / pad are baked into the captured launch
+  const std::string variant = std::to_string(knobs_generation()) + ":" + std::to_string(kn.split_ln) +
+                              std::to_string(kn.ffn_qkernel) + std::to_string(kn.device_step) +
+                              "b" + std::to_string(bt.eos) + "," + std::to_string(bt.pad);
+  const int per = n == big ? big : 1;
+  const GraphKey key{R, S, max_len, bt.K * 100000 + per, g.step, variant};
+  auto it = mm->graphs.find(key);
+  if (it == mm->graphs.end()) {
+    if (mm->graphs.size() >= 16) mm->clear_graphs();
+    hipGraph_t graph = nullptr;
+    HIPCHK(hipStreamBeginCapture(mm->gstream[0], hipStreamCaptureModeThreadLocal));
+    int rc = QTX_OK;
+    for (int t = 0; t < per && rc == QTX_OK; ++t)
+      rc = greedy_step_fused(m, g, R, S, max_len, nullptr, g.mask, mm->gstream[0], -1);
+    const hipError_t e = hipStreamEndCapture(mm->gstream[0], &graph);
+    if (rc != QTX_OK || e != hipSuccess) {
+      if (graph) (void)hipGraphDestroy(graph);
+      if (rc != QTX_OK) return rc;
+      HIPCHK(e);
+    }
+    hipGraphExec_t exec = nullptr;
+    const hipError_t e2 = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    HIPCHK(e2);
+    GraphEntry ent;
+    ent.execs.push_back(exec);
+    it = mm->graphs.emplace(key, std::move(ent)).first;
+  }
+  for (int r = 0; r < n / per; ++r) HIPCHK(hipGraphLaunch(it->second.execs[0], st));
+  if (!it->second.done) HIPCHK(hipEventCreateWithFlags(&it->second.done, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(it->second.done, st));
+  return QTX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t qtx_beam_workspace_size(const qtx_model* m, int32_t B, int32_t S, int32_t max_len,
+                               int32_t beam) {
+  if (!m || B <= 0 || S <= 0 || max_len < 1 || beam < 1 || beam > BEAM_MAXK) return 0;
+  return beam_ws(m->cfg, B, beam, S, max_len);
+}
+
+int32_t qtx_beam_decode(const qtx_model* m, const int64_t* src, const uint8_t* src_mask,
+                        int32_t B, int32_t S, int32_t max_len, int32_t beam, int64_t start,
+                        int64_t eos, int64_t pad, int32_t early_exit, int64_t* hyp_ids,
+                        float* hyp_score, int32_t* hyp_len, int32_t* steps_run, void* ws,
+                        size_t ws_bytes, void* stream) {
+  if (!m || !src || !src_mask || !hyp_ids || !hyp_score || !hyp_len || !ws)
+    return fail(QTX_E_INVALID, "null argument");
+  const qtx_config& c = m->cfg;
+  if (B <= 0 || S <= 0 || S > 512 || max_len < 1 || max_len > 512 || max_len > c.max_len ||
+      S > c.max_len)
+    return fail(QTX_E_INVALID, "bad shape B=%d S=%d max_len=%d", B, S, max_len);
+  if (const int lim = beam_limits(B, beam, c.tgt_vocab, start, eos, pad); lim != QTX_OK)
+    return fail(lim, "beam decode: 1 <= beam <= 8, beam <= tgt_vocab, start / eos / pad inside "
+                     "the vocabulary, eos != pad, B * beam * tgt_vocab < 2^30 (beam=%d eos=%lld "
+                     "pad=%lld)", beam, (long long)eos, (long long)pad);
+  if ((long)B * beam * max_len * c.d_model >= (1L << 30))
+    return fail(QTX_E_UNSUPPORTED, "beam decode: B * beam * max_len * d_model must be below 2^30");
+  if (knobs().dbg_tail) return fail(QTX_E_UNSUPPORTED, "beam decode: not with QTX_DBG_TAIL");
+  if (ws_bytes < beam_ws(c, B, beam, S, max_len)) return fail(QTX_E_WORKSPACE, "workspace too small");
+  dfault_forget(m, ws);
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar;
+  ar.base = (uint8_t*)ws; ar.cap = ws_bytes;
+  unsigned* cst = nullptr;
+  RC(call_status_begin(m, &cst, st));
+  BeamWS w = carve_beam(ar, c, B, beam, S, max_len);
+  w.tail.eos = (int)eos; w.tail.pad = (int)pad;
+  const int R = B * beam;
+  // every config decodes: the fused step where the greedy decode of R rows would take it
+  const bool fused = greedy_fused(c, S, max_len);
+  w.tail.grouped = fused;
+  w.g.beam = &w.tail;
+  w.g.enc.status = cst;
+  HIPCHK(hipMemcpyAsync(w.mask_b, src_mask, (size_t)B * S, hipMemcpyDeviceToDevice, st));
+  RC(beam_prologue(m, w, src, B, beam, S, start, fused, st));
+  // the steps in chunks of QTX_GRAPH_STEPS (default 8); with early_exit the rows still live
+  // are read back after each chunk (one 4-byte synchronising copy) and the decode stops at 0
+  const int total = max_len - 1, big = knobs().graph_steps > 0 ? knobs().graph_steps : 8;
+  int run = 0;
+  while (run < total) {
+    const int n = std::min(big, total - run);
+    RC(beam_steps(m, w, R, S, max_len, n, big, fused, st));
+    run += n;
+    if (early_exit && run < total) {
+      int live = 1;
+      HIPCHK(hipMemcpyAsync(&live, w.g.step + 3, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (live == 0) break;
+    }
+  }
+  const BeamState& bs = w.tail.st;
+  HIPCHK(launch_beam_backtrack(bs.bp_par, bs.bp_tok, B, beam, max_len, run, start, pad, hyp_ids, st));
+  HIPCHK(hipMemcpyAsync(hyp_score, bs.score, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(hyp_len, bs.len, (size_t)R * sizeof(int), hipMemcpyDeviceToDevice, st));
+  if (steps_run) *steps_run = run;
+  return QTX_OK;
+}
+
+int32_t qtx_beam_select(const qtx_model* m, const float* logits, int32_t B, int32_t beam,
+                        int64_t eos, int64_t pad, int32_t max_len, int32_t* step_dev,
+                        float* score, int32_t* fin, int32_t* len, int32_t* parent,
+                        int32_t* bp_par, int32_t* bp_tok, float* x_next, void* stream) {
+  if (!m || !logits || !step_dev || !score || !fin || !len || !parent || !bp_par || !bp_tok ||
+      !x_next)
+    return fail(QTX_E_INVALID, "null argument");
+  if (max_len < 1 || max_len > 512) return fail(QTX_E_INVALID, "max_len %d", max_len);
+  if (const int lim = beam_limits(B, beam, m->cfg.tgt_vocab, 0, eos, pad); lim != QTX_OK)
+    return fail(lim, "beam select: beam %d, eos %lld, pad %lld, tgt_vocab %d", beam,
+                (long long)eos, (long long)pad, m->cfg.tgt_vocab);
+  HIPCHK(launch_beam_select(logits, B, beam, m->cfg.tgt_vocab, (int)eos, (int)pad, max_len,
+                            step_dev, score, fin, len, parent, bp_par, bp_tok, m->tgt_lut, m->pe,
+                            m->cfg.max_len, x_next, (hipStream_t)stream));
+  return QTX_OK;
+}
+
+int32_t qtx_beam_reorder(int8_t* kc, int8_t* vc, float* skc, float* svc, int32_t B, int32_t beam,
+                         int32_t max_len, int32_t n_layers, int64_t k_ls, int64_t v_ls,
+                         int64_t s_ls, int32_t v_grouped, const int32_t* step_dev,
+                         const int32_t* parent, void* stream) {
+  if (!kc || !vc || !skc || !svc || !step_dev || !parent) return fail(QTX_E_INVALID, "null argument");
+  if (B <= 0 || beam < 1 || beam > BEAM_MAXK || max_len < 1 || max_len > 512 || n_layers < 1)
+    return fail(QTX_E_INVALID, "bad shape B=%d beam=%d max_len=%d layers=%d", B, beam, max_len,
+                n_layers);
+  const BeamGeom g{max_len, v_grouped ? 1 : 0};
+  if (k_ls < (int64_t)B * beam * g.k_row() || v_ls < (int64_t)B * beam * g.v_row() ||
+      s_ls < (int64_t)B * beam * g.s_row() || k_ls % 16 || v_ls % 16 || !aligned16(kc) ||
+      !aligned16(vc))
+    return fail(QTX_E_INVALID, "beam reorder: layer strides below B * beam rows, or codes not "
+                               "16-byte aligned");
+  HIPCHK(launch_beam_reorder(kc, vc, skc, svc, B, beam, max_len, n_layers, k_ls, v_ls, s_ls,
+                             g.grouped, step_dev, parent, (hipStream_t)stream));
   return QTX_OK;
 }
 

@@ -273,6 +273,32 @@ __device__ __forceinline__ float qlog(float x) {
   return fmaf((float)e, 0x1.62e43p-1f, p / q);
 }
 
+// One row's canonical log-softmax terms, by one wave (k_lsm_top2, k_beam_select): the maximum,
+// lse = qlog(lane-split sum of qexp(x - max)) over the 64-lane butterfly, and whether the row
+// is non-finite (a NaN or +inf, or only -inf: an all-NaN log-softmax; mx = lse = 0 then).
+// logp[v] = (x[v] - mx) - lse.  Wave-uniform results; the order is bit-exact by contract.
+// (Eight loads in flight: the first pass over a row pays the global-memory latency.)
+__device__ __forceinline__ void row_lse(const float* x, int V, int lane, float& mx, float& lse,
+                                        bool& bad) {
+  float lm = -3.0e38f;
+  bool nonfin = false, fin = false;
+#pragma unroll 8
+  for (int v = lane; v < V; v += 64) {
+    const float t = x[v];
+    lm = fmaxf(lm, t);
+    nonfin |= !(t < __builtin_inff());
+    fin |= t > -__builtin_inff();
+  }
+  bad = __ballot(nonfin) != 0ull || __ballot(fin) == 0ull;
+  mx = 0.0f; lse = 0.0f;
+  if (bad) return;
+  mx = wave_max(lm);
+  float ls = 0.0f;
+#pragma unroll 8
+  for (int v = lane; v < V; v += 64) ls = ls + qexp(x[v] - mx);
+  lse = qlog(wave_sum(ls));
+}
+
 // ---------------------------------------------------------------- shared-divisor division
 // Correctly rounded a / b for many a sharing one divisor b (Markstein): with
 // y = RN(1/b), q = RN(a*y), r = fma(-q, b, a) (exact), RN(q + r*y) == RN(a/b) provided

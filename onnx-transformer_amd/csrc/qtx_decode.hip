@@ -1931,4 +1931,338 @@ hipError_t launch_set_steps(int* step, int* gsteps, int G, int value, hipStream_
   return hipGetLastError();
 }
 
+
+// =====================================================================================
+// Beam search (include/qtx.h, beam search; qtx_api.hip beam_prologue / beam_steps /
+// qtx_beam_decode).  Rows r = b * K + k are the K hypotheses of sentence b.  Scalars lead the
+// parameter lists (preloaded); every offset is bounded on the host (launch_beam_select:
+// B * K * V < 2^30, V < 2^21, B * K < 2^21) and every position write checks its column.
+// =====================================================================================
+// The candidate (value, flat) as one 64-bit key whose unsigned order is the selection's total
+// order "larger value, then smaller flat": the value's monotone image in the high word, ~flat
+// in the low word.  Key 0 is the empty slot: below every candidate (-inf maps to 0x007fffff).
+// The image orders +0.0 above -0.0, which the order on values takes as equal.  The search never
+// forms a -0.0 (it needs (-0) + (-0), and the scores start at +0.0); a caller of the per-op
+// entry who passes a -0.0 score gets it ranked just below +0.0 and returned unchanged.
+__device__ __forceinline__ uint32_t beam_fkey(float v) {
+  const uint32_t b = __float_as_uint(v);
+  return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float beam_fval(uint32_t k) {
+  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned long long o = __shfl_xor(v, off, 64);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+// k_beam_select: one 1024-thread workgroup per sentence; the tail of the beam step, fused and
+// unfused (no LDS-resident vocabulary: the logits are read from global memory; V < 2^21 for the
+// 32-bit embedding offsets).  Waves 0 .. K-1 form their row's log-softmax terms (row_lse,
+// qtx_common.h); then every thread scans its stripe of the K * V candidates
+//   live row k:     (fl32(score[k] + logp[k][v]), k * V + v), a non-finite value taken as -inf
+//   finished row k: the single candidate (score[k], k * V + pad)
+// keeping its best KB keys in registers, and K rounds of a workgroup maximum (the winner
+// removed each round) give the K best in order.  Slot j takes the j-th: parent = flat / V,
+// token = flat % V, score = value, finished = parent finished or token == eos, length = s + 1
+// unless the parent was finished; back-pointers (parent, token) of step s; the next decoder
+// input tgt_embed(token) at position s + 1.  step[0]: the position s (read, then advanced by
+// the last workgroup to arrive), step[1]: arrival counter, step[2]: accumulator of the rows
+// still live, step[3]: their count after this step (what the host reads for the early exit).
+constexpr int BEAM_T = 1024;
+template <int KB>
+__global__ __launch_bounds__(BEAM_T) void k_beam_select(int V, int K, int eos, int pad,
+                                                        int max_len, int max_pos,
+                                                        const float* logits, int* step,
+                                                        float* score, int* fin, int* len,
+                                                        int* parent, int* bp_par, int* bp_tok,
+                                                        const float* lut, const float* pe,
+                                                        float* xnext) {
+  __shared__ float s_mx[BEAM_MAXK], s_lse[BEAM_MAXK], s_score[BEAM_MAXK];
+  __shared__ int s_bad[BEAM_MAXK], s_fin[BEAM_MAXK], s_len[BEAM_MAXK];
+  __shared__ unsigned long long red[2][BEAM_T / 64], win[BEAM_MAXK];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int R = gridDim.x * K;
+  const int s = *step;
+  if (tid < K) {
+    s_score[tid] = score[b * K + tid];
+    s_fin[tid] = fin[b * K + tid];
+    s_len[tid] = len[b * K + tid];
+  }
+  if (w < K) {
+    float mx, lse;
+    bool bad;
+    row_lse(logits + (size_t)(b * K + w) * V, V, lane, mx, lse, bad);
+    if (lane == 0) { s_mx[w] = mx; s_lse[w] = lse; s_bad[w] = bad ? 1 : 0; }
+  }
+  __syncthreads();
+  unsigned long long keys[KB];
+#pragma unroll
+  for (int i = 0; i < KB; ++i) keys[i] = 0ull;
+  auto offer = [&](float val, int flat) {
+    if (!(fabsf(val) < __builtin_inff())) val = -__builtin_inff();   // NaN, +-inf
+    const unsigned long long key =
+        ((unsigned long long)beam_fkey(val) << 32) | (unsigned long long)(~(uint32_t)flat);
+    if (key > keys[KB - 1]) {
+      keys[KB - 1] = key;
+#pragma unroll
+      for (int i = KB - 1; i > 0; --i)
+        if (keys[i] > keys[i - 1]) {
+          const unsigned long long t = keys[i]; keys[i] = keys[i - 1]; keys[i - 1] = t;
+        }
+    }
+  };
+  for (int k = 0; k < K; ++k) {
+    const float sc = s_score[k];
+    if (s_fin[k]) {                          // (block-uniform)
+      if (tid == 0) offer(sc, k * V + pad);
+      continue;
+    }
+    const float* x = logits + (size_t)(b * K + k) * V;
+    const float mx = s_mx[k], lse = s_lse[k];
+    const bool bad = s_bad[k] != 0;
+    for (int v = tid; v < V; v += BEAM_T)
+      offer(bad ? -__builtin_inff() : sc + ((x[v] - mx) - lse), k * V + v);
+  }
+  for (int j = 0; j < K; ++j) {
+    const unsigned long long h = wave_max_u64(keys[0]);
+    if (lane == 0) red[j & 1][w] = h;
+    __syncthreads();
+    unsigned long long g = 0ull;
+#pragma unroll
+    for (int i = 0; i < BEAM_T / 64; ++i) {
+      const unsigned long long o = red[j & 1][i];
+      g = o > g ? o : g;
+    }
+    if (keys[0] == g && g != 0ull) {         // the winner's owner drops it (keys are distinct)
+#pragma unroll
+      for (int i = 0; i + 1 < KB; ++i) keys[i] = keys[i + 1];
+      keys[KB - 1] = 0ull;
+    }
+    if (tid == 0) win[j] = g;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int live = 0;
+    for (int j = 0; j < K; ++j) {
+      const unsigned long long g = win[j];
+      const uint32_t flat = ~(uint32_t)g;
+      const int p = min((int)(flat / (uint32_t)V), K - 1), tok = (int)(flat % (uint32_t)V);
+      const int r = b * K + j;
+      const int pf = s_fin[p], nf = (pf || tok == eos) ? 1 : 0;
+      parent[r] = p;
+      score[r] = beam_fval((uint32_t)(g >> 32));
+      fin[r] = nf;
+      len[r] = pf ? s_len[p] : s + 1;
+      live += nf ? 0 : 1;
+      if (s >= 0 && s + 1 < max_len) {       // bounded (stale position)
+        bp_par[s * R + r] = p;
+        bp_tok[s * R + r] = tok;
+      }
+    }
+    // the rows still live, then the arrival: the last workgroup publishes the sum, advances
+    // the position (every workgroup has read it above) and re-arms both counters
+    atomicAdd(step + 2, live);
+    __threadfence();
+    const unsigned tk = atomicAdd(reinterpret_cast<unsigned*>(step + 1), 1u);
+    if (tk == gridDim.x - 1) {
+      __threadfence();
+      step[3] = atomicExch(step + 2, 0);
+      step[0] = s + 1;
+      step[1] = 0;
+    }
+  }
+  // next decoder inputs: tgt_embed(token) at position s + 1 (embeddings.py:12-13), 128 threads
+  // per slot
+  const int j = tid >> 7, q = tid & 127;
+  if (j < K) {
+    const int tok = (int)((~(uint32_t)win[j]) % (uint32_t)V);
+    const float sc = 0x1.6a09e6p+4f;
+    const float4 e = ld_at(reinterpret_cast<const float4*>(lut), 16u * (unsigned)(tok * 128 + q));
+    const float4 pr = ld_at(reinterpret_cast<const float4*>(pe),
+                            16u * (unsigned)(max(min(s + 1, max_pos - 1), 0) * 128 + q));
+    st_at(reinterpret_cast<float4*>(xnext), 16u * (unsigned)((b * K + j) * 128 + q),
+          make_float4(e.x * sc + pr.x, e.y * sc + pr.y, e.z * sc + pr.z, e.w * sc + pr.w));
+  }
+}
+
+hipError_t launch_beam_select(const float* logits, int B, int K, int V, int eos, int pad,
+                              int max_len, int* step, float* score, int* fin, int* len,
+                              int* parent, int* bp_par, int* bp_tok, const float* lut,
+                              const float* pe, int max_pos, float* xnext, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (K < 1 || K > BEAM_MAXK || K > V || eos < 0 || eos >= V || pad < 0 || pad >= V ||
+      max_len < 1 || max_pos < 1 || (long)B * K * V >= (1L << 30) ||
+      (long)B * K * max_len >= (1L << 30) ||
+      V >= (1 << 21) || (long)B * K >= (1L << 21))   // 16 * (row * 128 + q) in 32 bits
+    return hipErrorInvalidValue;
+#define QTX_BEAM_SEL(KB)                                                                      \
+  k_beam_select<KB><<<dim3(B), dim3(BEAM_T), 0, st>>>(V, K, eos, pad, max_len, max_pos,       \
+                                                      logits, step, score, fin, len, parent, \
+                                                      bp_par, bp_tok, lut, pe, xnext)
+  if (K == 1) QTX_BEAM_SEL(1);
+  else if (K == 2) QTX_BEAM_SEL(2);
+  else if (K <= 4) QTX_BEAM_SEL(4);
+  else QTX_BEAM_SEL(8);
+#undef QTX_BEAM_SEL
+  return hipGetLastError();
+}
+
+// k_beam_reorder: every layer's self K/V caches of slot j become those of its parent, in
+// place, one launch for all layers.  A row's cache is four contiguous regions (qtx_beam.h
+// BeamGeom); the same byte offset in all K regions of a sentence is owned by ONE thread, which
+// loads its K chunks and then stores them by parent — no two threads touch the same byte, so
+// there is no barrier and no second copy of the caches.  Only the valid prefix moves: positions
+// 0 .. n-1 with n = step[0] (the select has advanced it to the count of cached positions).
+// Workgroup (c, b, l) = blockIdx.x = (l * B + b) * nblk + c; chunk index c * 256 + tid runs
+// over the K, V, K-scale and V-scale chunks of (l, b).  l_* : layer strides.
+__global__ __launch_bounds__(256) void k_beam_reorder(int K, int max_len, int grouped, int B,
+                                                      int nblk, long k_ls, long v_ls, long s_ls,
+                                                      const int* step, const int* parent,
+                                                      int8_t* kc, int8_t* vc, float* skc,
+                                                      float* svc) {
+  const int c = blockIdx.x % nblk, lb = blockIdx.x / nblk, b = lb % B, l = lb / B;
+  const BeamGeom g{max_len, grouped};
+  const int n = g.clamp(*step);
+  const long i = (long)c * 256 + threadIdx.x;
+  int p[BEAM_MAXK];
+  bool ident = true;
+#pragma unroll
+  for (int j = 0; j < BEAM_MAXK; ++j) {
+    p[j] = j < K ? min(max(parent[b * K + min(j, K - 1)], 0), K - 1) : j;
+    ident &= p[j] == j;
+  }
+  if (ident) return;
+  const BeamGeom::Chunk ck = g.locate(n, i);
+  if (ck.region == BEAM_NONE) return;
+  const size_t r0 = (size_t)b * K;
+  if (ck.region == BEAM_K || ck.region == BEAM_V) {
+    const bool isk = ck.region == BEAM_K;
+    const size_t row = isk ? g.k_row() : g.v_row();
+    uint8_t* base = reinterpret_cast<uint8_t*>(isk ? kc : vc) + (size_t)l * (isk ? k_ls : v_ls) +
+                    r0 * row + (size_t)ck.off;
+    uint4 ch[BEAM_MAXK];
+#pragma unroll
+    for (int j = 0; j < BEAM_MAXK; ++j)
+      if (j < K) ch[j] = *reinterpret_cast<const uint4*>(base + j * row);
+#pragma unroll
+    for (int j = 0; j < BEAM_MAXK; ++j)
+      if (j < K && p[j] != j) {
+        uint4 v = ch[0];
+#pragma unroll
+        for (int q = 1; q < BEAM_MAXK; ++q)
+          if (p[j] == q) v = ch[q];
+        *reinterpret_cast<uint4*>(base + j * row) = v;
+      }
+    return;
+  }
+  float* base = (ck.region == BEAM_SK ? skc : svc) + (size_t)l * s_ls + r0 * g.s_row() + ck.off;
+  float ch[BEAM_MAXK];
+#pragma unroll
+  for (int j = 0; j < BEAM_MAXK; ++j)
+    if (j < K) ch[j] = base[j * g.s_row()];
+#pragma unroll
+  for (int j = 0; j < BEAM_MAXK; ++j)
+    if (j < K && p[j] != j) {
+      float v = ch[0];
+#pragma unroll
+      for (int q = 1; q < BEAM_MAXK; ++q)
+        if (p[j] == q) v = ch[q];
+      base[j * g.s_row()] = v;
+    }
+}
+
+hipError_t launch_beam_reorder(int8_t* kc, int8_t* vc, float* skc, float* svc, int B, int K,
+                               int max_len, int L, long k_ls, long v_ls, long s_ls, int grouped,
+                               const int* step, const int* parent, hipStream_t st) {
+  if (B <= 0 || L <= 0 || K == 1) return hipSuccess;   // one hypothesis: nothing to permute
+  const BeamGeom g{max_len, grouped ? 1 : 0};
+  if (K < 1 || K > BEAM_MAXK || max_len < 1 || max_len > 512 ||
+      k_ls < (long)B * K * g.k_row() || v_ls < (long)B * K * g.v_row() ||
+      s_ls < (long)B * K * g.s_row() || (k_ls | v_ls) % 16 != 0 ||
+      (reinterpret_cast<uintptr_t>(kc) | reinterpret_cast<uintptr_t>(vc)) % 16 != 0)
+    return hipErrorInvalidValue;
+  const long nblk = (g.chunks(max_len) + 255) / 256;
+  if (nblk * B * L >= (1L << 31)) return hipErrorInvalidValue;
+  k_beam_reorder<<<dim3((unsigned)(nblk * B * L)), dim3(256), 0, st>>>(
+      K, max_len, g.grouped, B, (int)nblk, k_ls, v_ls, s_ls, step, parent, kc, vc, skc, svc);
+  return hipGetLastError();
+}
+
+// k_beam_rep: region r of out (n elements) = region r / K of in: the cross K/V, their scales
+// and the source mask replicated from the B sentences to the B * K hypotheses, once per decode.
+template <class T>
+__global__ __launch_bounds__(256) void k_beam_rep(int K, long n, const T* in, T* out) {
+  const long i = (long)blockIdx.y * 256 + threadIdx.x;
+  const size_t r = blockIdx.x;
+  if (i < n) out[r * n + i] = in[(r / K) * n + i];
+}
+
+hipError_t launch_beam_rep(const void* in, void* out, int B, int K, long bytes, hipStream_t st) {
+  if (B <= 0 || bytes <= 0) return hipSuccess;
+  if (K < 1 || bytes >= (1L << 30)) return hipErrorInvalidValue;
+  const bool v16 = bytes % 16 == 0 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const long n = v16 ? bytes / 16 : bytes;
+  const dim3 grid((unsigned)(B * K), (unsigned)((n + 255) / 256));
+  if (v16)
+    k_beam_rep<uint4><<<grid, dim3(256), 0, st>>>(K, n, static_cast<const uint4*>(in), static_cast<uint4*>(out));
+  else
+    k_beam_rep<uint8_t><<<grid, dim3(256), 0, st>>>(K, n, static_cast<const uint8_t*>(in), static_cast<uint8_t*>(out));
+  return hipGetLastError();
+}
+
+// k_beam_init: the search state before step 0 — score 0 on slot 0 and -inf on the others, no
+// row finished, length 0 — and the four step words zeroed.
+__global__ __launch_bounds__(256) void k_beam_init(int R, int K, float* score, int* fin, int* len,
+                                                   int* parent, int* step) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r < 4) step[r] = 0;
+  if (r >= R) return;
+  score[r] = r % K == 0 ? 0.0f : -__builtin_inff();
+  fin[r] = 0; len[r] = 0; parent[r] = r % K;
+}
+
+hipError_t launch_beam_init(int B, int K, float* score, int* fin, int* len, int* parent,
+                            int* step, hipStream_t st) {
+  if (B <= 0 || K < 1) return hipErrorInvalidValue;
+  const int R = B * K;
+  k_beam_init<<<dim3((R + 255) / 256), dim3(256), 0, st>>>(R, K, score, fin, len, parent, step);
+  return hipGetLastError();
+}
+
+// k_beam_backtrack: the histories from the back-pointers of the nsteps steps that ran: row r
+// of out [R][max_len] = start, then the tokens along slot r's ancestry, then pad.
+__global__ __launch_bounds__(64) void k_beam_backtrack(int R, int K, int max_len, int nsteps,
+                                                       long long start, long long pad,
+                                                       const int* bp_par, const int* bp_tok,
+                                                       int64_t* out) {
+  const int r = blockIdx.x * 64 + threadIdx.x;
+  if (r >= R) return;
+  int64_t* o = out + (size_t)r * max_len;
+  o[0] = start;
+  for (int t = nsteps + 1; t < max_len; ++t) o[t] = pad;
+  int cur = r;
+  for (int t = nsteps - 1; t >= 0; --t) {
+    o[t + 1] = bp_tok[t * R + cur];
+    cur = (cur / K) * K + min(max(bp_par[t * R + cur], 0), K - 1);
+  }
+}
+
+hipError_t launch_beam_backtrack(const int* bp_par, const int* bp_tok, int B, int K, int max_len,
+                                 int nsteps, long long start, long long pad, int64_t* out,
+                                 hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (K < 1 || max_len < 1 || nsteps < 0 || nsteps > max_len - 1 ||
+      (long)B * K * max_len >= (1L << 30))
+    return hipErrorInvalidValue;
+  const int R = B * K;
+  k_beam_backtrack<<<dim3((R + 63) / 64), dim3(64), 0, st>>>(R, K, max_len, nsteps, start, pad,
+                                                            bp_par, bp_tok, out);
+  return hipGetLastError();
+}
+
 }  // namespace qtx

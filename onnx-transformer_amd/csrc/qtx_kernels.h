@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qtx_beam.h"
+
 namespace qtx {
 
 enum : int {
@@ -281,6 +283,30 @@ hipError_t launch_dfault_tail(const int64_t* rec_ids, const float* rec_logp, int
                               int* changed, hipStream_t st);
 hipError_t launch_causal_mask(uint8_t* mask, int T, hipStream_t st);
 hipError_t launch_set_steps(int* step, int* gsteps, int G, int value, hipStream_t st);
+// Beam search (csrc/qtx_decode.hip; semantics: include/qtx.h, beam search).  Rows r = b * K + k.
+//   select:  the tail of a beam step on logits [B*K][V]: per sentence the K best of the K * V
+//            candidates; rewrites score / fin / len [B*K] in place, writes parent [B*K], the
+//            back-pointers bp_par / bp_tok [max_len-1][B*K] at column step[0], the next inputs
+//            xnext [B*K][512], and the step words (step [4]: position, arrival counter, live
+//            accumulator, rows still live).  1 <= K <= BEAM_MAXK, K <= V, B * K * V < 2^30.
+//   reorder: every layer's self K/V cache prefix (step[0] positions) of slot j := its parent's,
+//            in place (qtx_beam.h BeamGeom; k_ls / v_ls bytes and s_ls floats between layers)
+//   rep:     region r of out = region r / K of in (`bytes` each), r < B * K
+//   init:    score (0, -inf, ...), fin 0, len 0, parent identity, step words 0
+//   backtrack: out int64 [B*K][max_len] = start, the nsteps tokens of each slot's ancestry, pad
+hipError_t launch_beam_select(const float* logits, int B, int K, int V, int eos, int pad,
+                              int max_len, int* step, float* score, int* fin, int* len,
+                              int* parent, int* bp_par, int* bp_tok, const float* lut,
+                              const float* pe, int max_pos, float* xnext, hipStream_t st);
+hipError_t launch_beam_reorder(int8_t* kc, int8_t* vc, float* skc, float* svc, int B, int K,
+                               int max_len, int L, long k_ls, long v_ls, long s_ls, int grouped,
+                               const int* step, const int* parent, hipStream_t st);
+hipError_t launch_beam_rep(const void* in, void* out, int B, int K, long bytes, hipStream_t st);
+hipError_t launch_beam_init(int B, int K, float* score, int* fin, int* len, int* parent,
+                            int* step, hipStream_t st);
+hipError_t launch_beam_backtrack(const int* bp_par, const int* bp_tok, int B, int K, int max_len,
+                                 int nsteps, long long start, long long pad, int64_t* out,
+                                 hipStream_t st);
 hipError_t launch_rows(const RowArgs& a, hipStream_t st);
 hipError_t launch_attention(const AttnArgs& a, hipStream_t st);
 hipError_t launch_embed(const int64_t* ids, long ids_bs, int B, int T, const int* pos_dev,

@@ -552,22 +552,14 @@ __global__ __launch_bounds__(64) void k_lsm_top2(const float* logits, int V, int
                                                  int64_t* top_ids, float* top_logp, long top_bs) {
   const int m = blockIdx.x, lane = threadIdx.x;
   const float* x = logits + (long)m * V;
-  float lm = -3.0e38f;
-  bool nonfin = false, fin = false;
-  for (int v = lane; v < V; v += 64) {
-    lm = fmaxf(lm, x[v]);
-    nonfin |= !(x[v] < __builtin_inff());
-    fin |= x[v] > -__builtin_inff();
-  }
+  float mx, lse;
+  bool bad;
+  row_lse(x, V, lane, mx, lse, bad);
   Top2 top;
-  if (__ballot(nonfin) != 0ull || __ballot(fin) == 0ull) {     // wave-uniform
+  if (bad) {                                                   // wave-uniform
     top.i1 = 0; top.i2 = 1;
     top.v1 = top.v2 = __builtin_nanf("");
   } else {
-    const float mx = wave_max(lm);
-    float ls = 0.0f;
-    for (int v = lane; v < V; v += 64) ls = ls + qexp(x[v] - mx);
-    const float lse = qlog(wave_sum(ls));
     for (int v = lane; v < V; v += 64) top.add((x[v] - mx) - lse, v);
     wave_top2(top);
   }

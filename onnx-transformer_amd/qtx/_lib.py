@@ -103,6 +103,11 @@ SIGNATURES = {
                                        I32, P]),
     "qtx_greedy_dfault_resume": (I32, [P, I32, I32, I32, P, P, P, P, P, P, SZ, FP, I32,
                                        C.POINTER(I32), P]),
+    "qtx_beam_workspace_size": (SZ, [P, I32, I32, I32, I32]),
+    "qtx_beam_decode": (I32, [P, P, P, I32, I32, I32, I32, I64, I64, I64, I32, P, P, P,
+                              C.POINTER(I32), P, SZ, P]),
+    "qtx_beam_select": (I32, [P, P, I32, I32, I64, I64, I32, P, P, P, P, P, P, P, P, P]),
+    "qtx_beam_reorder": (I32, [P, P, P, P, I32, I32, I32, I32, I64, I64, I64, I32, P, P, P]),
     "qtx_generator_top2": (I32, [P, P, I32, P, P, P, SZ, P]),
     "qtx_decode_top2_embed": (I32, [P, P, I32, P, I64, P, P, P, P, P]),
     "qtx_decode_generator": (I32, [P, P, I32, P, P, P]),

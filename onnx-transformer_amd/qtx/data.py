@@ -117,6 +117,13 @@ def score(ids, tgt, vocab_tgt: Vocab) -> EvalResult:
                       np.asarray(ids))
 
 
+def beam_decoder(model, **beam_kwargs):
+    """A ``decode`` callable for evaluate(): the best hypothesis per sentence of
+    qtx.decode.beam_decode(model, ..., **beam_kwargs) (beam_size, length_penalty, ...)."""
+    from .decode import beam_decode
+    return lambda s, m, n: beam_decode(model, s, m, n, BOS, **beam_kwargs).ids[:, 0]
+
+
 def evaluate(model, pairs, vocab_src: Vocab, vocab_tgt: Vocab, batch_size: int = 32,
              max_padding: int = 128, max_len: int = 72, decode=None) -> EvalResult:
     """Greedy-decode ``pairs`` in file order, ``batch_size`` sentences per call, and score

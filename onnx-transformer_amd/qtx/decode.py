@@ -13,7 +13,7 @@ import dataclasses
 import numpy as np
 
 from .model import QtxModel, to_u8_mask
-from .weights import PAD
+from .weights import EOS, PAD
 
 
 @dataclasses.dataclass
@@ -66,6 +66,61 @@ def greedy_decode(model: QtxModel, src, src_mask, max_len: int, start_symbol: in
         ys, top_ids, top_logp = out
         return to_host(ys), Scores(to_host(top_ids), to_host(top_logp))
     return to_host(out)
+
+
+@dataclasses.dataclass
+class BeamResult:
+    """beam_decode's result (numpy or torch, like the src it came from).  Ranked: ``ids`` int64
+    [B, n_best, max_len], ``scores`` float64 [B, n_best] (score / max(len, 1) **
+    length_penalty) and ``lengths`` int32 [B, n_best] (tokens after the start symbol, the EOS
+    included).  As the library left them, in search order (best raw score first): ``hyp_ids``
+    [B, beam, max_len], ``hyp_score`` float32 [B, beam] (cumulative log-probability),
+    ``hyp_len`` int32 [B, beam].  ``steps_run``: the decoder steps launched."""
+    ids: object
+    scores: object
+    lengths: object
+    hyp_ids: object
+    hyp_score: object
+    hyp_len: object
+    steps_run: int
+
+
+def rank_hypotheses(hyp_score, hyp_len, length_penalty: float = 0.0):
+    """Per sentence the order of the hypotheses by score / max(len, 1) ** length_penalty in
+    float64, descending and stable (length_penalty = 0 keeps the library's order).
+    hyp_score [B, K], hyp_len [B, K] (numpy) -> (order int64 [B, K], ranked scores float64)."""
+    s = np.asarray(hyp_score, np.float64) / np.maximum(np.asarray(hyp_len), 1) ** float(length_penalty)
+    order = np.argsort(-s, axis=-1, kind="stable")
+    return order, np.take_along_axis(s, order, axis=-1)
+
+
+def beam_decode(model: QtxModel, src, src_mask, max_len: int, start_symbol: int = 0,
+                beam_size: int = 4, eos: int = EOS, pad: int = PAD, length_penalty: float = 0.0,
+                n_best: int = 1, early_exit: bool = True) -> BeamResult:
+    """Beam search with EOS stop (include/qtx.h, beam search): src int64 [B,S] (numpy or
+    torch), src_mask [B,1,S] bool -> BeamResult.  The search itself knows no length
+    normalisation; the hypotheses are ranked here (rank_hypotheses) and the n_best first kept."""
+    import torch
+    if not 1 <= int(n_best) <= int(beam_size):
+        raise ValueError(f"n_best {n_best} outside 1 .. beam_size {beam_size}")
+    was_numpy = isinstance(src, np.ndarray)
+    src_t = torch.from_numpy(np.ascontiguousarray(src)) if was_numpy else src
+    B, S = src_t.shape
+    srcd = src_t.to(model.device, torch.int64).contiguous()
+    md = to_u8_mask(src_mask, model.device).reshape(B, S)
+    hyp_ids, hyp_score, hyp_len, steps = model.beam(srcd, md, max_len=max_len, start=start_symbol,
+                                                    beam_size=beam_size, eos=eos, pad=pad,
+                                                    early_exit=early_exit)
+    model.check()
+    hi, hs, hl = hyp_ids.cpu().numpy(), hyp_score.cpu().numpy(), hyp_len.cpu().numpy()
+    order, ranked = rank_hypotheses(hs, hl, length_penalty)
+    order, ranked = order[:, :n_best], ranked[:, :n_best]
+    ids = np.take_along_axis(hi, order[:, :, None], axis=1)
+    lens = np.take_along_axis(hl, order, axis=1)
+    out = (ids, ranked, lens, hi, hs, hl)
+    if not was_numpy:
+        out = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(src_t.device) for a in out)
+    return BeamResult(*out, steps_run=steps)
 
 
 def greedy_decode_fault(model: QtxModel, src, src_mask, max_len: int, start_symbol: int = 0,

@@ -12,7 +12,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from .weights import ModelConfig, positional_table, tensor_order
+from .weights import EOS, PAD, ModelConfig, positional_table, tensor_order
 
 
 def _torch():
@@ -178,6 +178,29 @@ class QtxModel:
                       S, max_len, int(start), _ptr(ids), _ptr(ws), ws.numel(),
                       C.byref(fault.to_c()), _stream(self.device))
         return ids
+
+    @_on_device
+    def beam(self, src, src_mask_u8, max_len: int = 72, start: int = 0, beam_size: int = 4,
+             eos: int = EOS, pad: int = PAD, early_exit: bool = True):
+        """Beam search with EOS stop (qtx_beam_decode).  src int64 [B,S], src_mask [B,S] u8 ->
+        (hyp_ids int64 [B,beam,max_len], hyp_score f32 [B,beam], hyp_len int32 [B,beam]) on
+        the device, in search order (best raw score first), and steps_run (int): the decoder
+        steps launched.  early_exit: stop once every hypothesis has ended (the host reads one
+        word back every QTX_GRAPH_STEPS steps); the outputs do not depend on it."""
+        torch = _torch()
+        B, S = src.shape
+        K = int(beam_size)
+        hyp_ids = torch.empty((B, max(K, 0), max_len), dtype=torch.int64, device=self.device)
+        hyp_score = torch.empty((B, max(K, 0)), dtype=torch.float32, device=self.device)
+        hyp_len = torch.empty((B, max(K, 0)), dtype=torch.int32, device=self.device)
+        steps = C.c_int32(0)
+        nb = _lib.lib().qtx_beam_workspace_size(self.handle, B, S, max_len, K)
+        ws = self.workspace(nb)
+        _lib.call("qtx_beam_decode", self.handle, _ptr(src), _ptr(src_mask_u8), B, S, max_len, K,
+                  int(start), int(eos), int(pad), 1 if early_exit else 0, _ptr(hyp_ids),
+                  _ptr(hyp_score), _ptr(hyp_len), C.byref(steps), _ptr(ws), ws.numel(),
+                  _stream(self.device))
+        return hyp_ids, hyp_score, hyp_len, int(steps.value)
 
     @_on_device
     def dfault_workspace(self, B: int, S: int, max_len: int):
