@@ -19,6 +19,9 @@
  *   qtx_greedy_decode_scored, qtx_generator_top2
  *                        <- the campaign's torch.topk(prob, 2, dim=1) of a step's generator
  *                           output           parallelized_inject_onnx_transformer.py:718-740
+ *   qtx_score_targets, qtx_score_rows, qtx_score_logits
+ *                        <- EncoderDecoder.forward on Batch.tgt / tgt_y + log_softmax
+ *                           encoder_decoder.py:19-23, batch.py:17-30, generator.py:15
  *   qtx_row_quant        <- quantize_activation_per_token_absmax / quantize_weight_per_channel_absmax
  *                                                            quant_linear.py:30-43 / :5-17
  *   qtx_layernorm_quant  <- LayerNorm.forward (+ the next W8A8Linear's act quant)
@@ -357,6 +360,66 @@ int32_t qtx_beam_decode(const qtx_model* m, const int64_t* src, const uint8_t* s
                         int64_t eos, int64_t pad, int32_t early_exit, int64_t* hyp_ids,
                         float* hyp_score, int32_t* hyp_len, int32_t* steps_run, void* ws,
                         size_t ws_bytes, void* stream);
+
+/* ---- teacher-forced target scoring: per-token log-prob, rank and top 2 ----
+ * The reference's forward pass on a given target: EncoderDecoder.forward(src, tgt, src_mask,
+ * tgt_mask) (encoder_decoder.py:19-23) with Batch.tgt = tgt[:, :-1], Batch.tgt_y = tgt[:, 1:]
+ * and make_std_mask (batch.py:17-30, train.py:28-30), then generator.py:15's log_softmax.
+ * src int64 [B, S], src_mask uint8 [B, S]; tgt int64 [R, L], R = B * K with K = tgt_per_src
+ * >= 1, row r a target of sentence r / K (the beam search's numbering); L >= 2, T = L - 1.
+ * The decoder's input is tgt[:, :T] (ids outside the vocabulary clamped, as qtx_embed), the
+ * labels are y = tgt[:, 1:].  Target mask: pad >= 0: keep[r, i, j] = j <= i and
+ * tgt[r, j] != pad (batch.py:25-30, a [R, T, T] mask); pad < 0: the causal mask alone.
+ * One full-prefix decoder pass over all R * T positions per trial; the results equal the
+ * KV-cached steps' (causal invariance).  Per position (r, t), x = the logits row of the final
+ * LayerNorm's output in the canonical generator order and logp its canonical log-softmax
+ * (scored decode above: qlog, not the platform logf):
+ *   tok_logp  logp[y]
+ *   rank      the number of v with logp[v] > logp[y], or logp[v] == logp[y] and v < y: the
+ *             scored decode's total order, so rank 0 <=> y == top 1 and rank 1 <=> y == top 2
+ *   top_ids / top_logp  the row's top 2 under the scored decode's rules
+ *   a non-finite row (scored decode's definition): tok_logp NaN, rank -1, top ids (0, 1), both
+ *   values NaN.  A label outside [0, tgt_vocab): tok_logp NaN, rank -1, nothing outside the
+ *   row is read; the top 2 are still the row's.
+ * Positions whose label is pad are computed and written like any other (the caller masks).
+ * Trials: trial 0 is fault-free, trial n = 1 .. n_faults applies faults[n - 1] (HOST array)
+ * alone; every output has a leading trial axis of n_faults + 1, and a trial's result equals a
+ * stand-alone call with that one fault.  An encoder fault (module 0) reruns the encoder and
+ * the cross K/V with the fault into buffers of their own; a decoder fault runs one faulty pass
+ * on the golden memory, its row indexing the [R * T] tokens (QTX_LIN_CK / CV: [B * S], on a
+ * cross copy of its own).  The golden memory and cross K/V serve every trial.
+ * The encoder and the cross K/V GEMM run once on the B sentences (replicated to the R rows
+ * when K > 1); the generator runs on chunks of rows, each followed by the scoring kernel
+ * (csrc/qtx_kernels.hip k_lsm_score): no [R * T, tgt_vocab] log-probabilities are written.
+ * Eager launches, no graphs.
+ * Writes exactly tok_logp float and rank int32 [n_faults + 1, R, T], top_ids int64 and
+ * top_logp float [n_faults + 1, R, T, 2] (both NULL: not wanted).
+ * Refused before anything is launched: L < 2, K < 1, S or T above 512 or the positional
+ * table, n_faults < 0, n_faults > 0 with faults NULL, a fault of kind NONE, a coordinate
+ * outside the trial's shapes: QTX_E_INVALID; R * T * d_model >= 2^30, any fault with 4-bit
+ * weights or K > 1 (the two row numberings would disagree): QTX_E_UNSUPPORTED; a short
+ * workspace: QTX_E_WORKSPACE.  ws: qtx_score_workspace_size bytes. */
+size_t qtx_score_workspace_size(const qtx_model* m, int32_t B, int32_t S, int32_t L,
+                                int32_t tgt_per_src, int32_t n_faults);
+int32_t qtx_score_targets(const qtx_model* m, const int64_t* src, const uint8_t* src_mask,
+                          int32_t B, int32_t S, const int64_t* tgt, int32_t L,
+                          int32_t tgt_per_src, int64_t pad, const qtx_fault* faults,
+                          int32_t n_faults, float* tok_logp, int32_t* rank, int64_t* top_ids,
+                          float* top_logp, void* ws, size_t ws_bytes, void* stream);
+/* The scoring tail alone (generator.py:15 on given labels): logits float [M, V], y int64 [M]
+ * -> tok_logp, rank [M], top_ids / top_logp [M, 2] (both NULL: not wanted), semantics above.
+ * V >= 2, else QTX_E_INVALID.  Writes exactly those outputs. */
+int32_t qtx_score_logits(const float* logits, const int64_t* y, int32_t M, int32_t V,
+                         float* tok_logp, int32_t* rank, int64_t* top_ids, float* top_logp,
+                         void* stream);
+/* The generator in chunks of rows plus that tail (generator.py:14-15): x float [M, d_model]
+ * (the final LayerNorm applied), y int64 [M].  ws holds one chunk's logits: the chunk is
+ * min(M, floor(ws_bytes / (4 * tgt_vocab)) & ~15) rows; fewer than 16 rows' worth:
+ * QTX_E_WORKSPACE.  The results do not depend on the chunk.  Writes exactly the outputs named
+ * above (and ws).  qtx_score_targets runs the same function per trial. */
+int32_t qtx_score_rows(const qtx_model* m, const float* x, int32_t M, const int64_t* y,
+                       float* tok_logp, int32_t* rank, int64_t* top_ids, float* top_logp,
+                       void* ws, size_t ws_bytes, void* stream);
 
 /* Embeddings + positional encoding: which = 0 (src) / 1 (tgt); ids int64 [B,T] ->
  * out [B,T,d], positions pos0 .. pos0+T-1. */

@@ -2584,6 +2584,242 @@ int32_t qtx_beam_reorder(int8_t* kc, int8_t* vc, float* skc, float* svc, int32_t
 
 }  // extern "C"
 
+// =======================================================================================
+// Teacher-forced target scoring (include/qtx.h: qtx_score_targets)
+// =======================================================================================
+namespace {
+
+// One generator chunk's logits at the model-level call: at most 64 MiB, there only to bound
+// the workspace whatever R * T is.  Larger chunks measured faster all the way to one launch
+// (cfg2's shape, 2272 rows, V = 4444: generator + tail 1.043 / 0.371 / 0.235 / 0.204 ms with
+// chunks of 64 / 256 / 928 / all rows, profiles/score_bench.md).
+constexpr size_t SCORE_CHUNK_BYTES = (size_t)64 << 20;
+
+// Rows of logits per generator launch that `bytes` of workspace hold: a multiple of 16 (the
+// generator's row block) with chunk * V below 2^30 (its 32-bit offsets), at most M; 0 when
+// not even 16 rows fit.
+int score_chunk(size_t bytes, int V, long M) {
+  size_t rows = bytes / (4 * (size_t)V);
+  rows = std::min(rows, (size_t)(((1L << 30) - 1) / V)) & ~(size_t)15;
+  if (rows < 16) return 0;
+  return (int)std::min(rows, (size_t)M);
+}
+
+// what the model-level call reserves for a chunk's logits
+size_t score_logits_bytes(int V, long M) {
+  const size_t rows = std::max((size_t)16, (SCORE_CHUNK_BYTES / (4 * (size_t)V)) & ~(size_t)15);
+  return std::min(rows, ((size_t)M + 15) & ~(size_t)15) * (size_t)V * 4;
+}
+
+// The generator on x [M, D] (the final LayerNorm already applied) in chunks of `chunk` rows,
+// each followed by k_lsm_score on the chunk's logits; label of row g: y[(g / y_t) * y_l + g % y_t].
+int score_rows_run(const qtx_model* m, const float* x, long M, const int64_t* y, int y_t, int y_l,
+                   float* tok_logp, int* rank, int64_t* top_ids, float* top_logp, float* logits,
+                   int chunk, hipStream_t st) {
+  const qtx_config& c = m->cfg;
+  for (long r0 = 0; r0 < M; r0 += chunk) {
+    const int n = (int)std::min((long)chunk, M - r0);
+    HIPCHK(launch_generator_mfma(x + r0 * c.d_model, c.d_model, n, nullptr, nullptr, m->gen_wt,
+                                 m->gen_b, c.tgt_vocab, logits, st));
+    HIPCHK(launch_lsm_score(logits, n, c.tgt_vocab, y, r0, y_t, y_l, tok_logp, rank, top_ids,
+                            top_logp, st));
+  }
+  return QTX_OK;
+}
+
+struct ScoreWS {
+  Scratch enc, dec;     // B * S source rows; R * T target rows
+  CrossKV cross;        // the B sentences' golden cross K/V
+  CrossKV fcross;       // a faulty trial's own copy (encoder fault, CK / CV fault)
+  CrossKV rcross;       // tgt_per_src > 1: the golden ones replicated to the R rows
+  float* memory;        // [B * S, D] golden
+  float* fmemory;       // an encoder-fault trial's
+  uint8_t* rmask;       // [R, S] the source mask per row (tgt_per_src > 1)
+  uint8_t* tmask;       // [R, T, T] (pad < 0: [T, T])
+  float* out;           // [R * T, D] the decoder's output
+  float* logits;        // one chunk
+  size_t logits_bytes;
+};
+
+ScoreWS carve_score(Arena& ar, const qtx_config& c, long B, long S, long L, long K, long nf) {
+  ScoreWS w;
+  const size_t D = c.d_model, NL = c.n_layers, R = (size_t)(B * K), T = (size_t)(L - 1);
+  const size_t Ms = (size_t)(B * S);
+  w.enc = carve_scratch(ar, c, (long)Ms);
+  w.dec = carve_scratch(ar, c, (long)(R * T));
+  w.cross = carve_cross(ar, c, (long)Ms);
+  w.memory = ar.take<float>(Ms * D);
+  w.fmemory = nullptr;
+  if (nf > 0) {
+    w.fcross = carve_cross(ar, c, (long)Ms);
+    w.fmemory = ar.take<float>(Ms * D);
+  }
+  w.rmask = nullptr;
+  if (K > 1) {   // the layout of carve_cross (tile 2 l + {0: K, 1: V}), R * S rows
+    w.rcross.am8 = nullptr; w.rcross.sam = nullptr; w.rcross.y = nullptr;
+    int8_t* kv = ar.take<int8_t>(2 * NL * R * S * D);
+    float* sc = ar.take<float>(2 * NL * R * S);
+    for (size_t l = 0; l < NL; ++l) {
+      w.rcross.k8.push_back(kv ? kv + 2 * l * R * S * D : nullptr);
+      w.rcross.v8.push_back(kv ? kv + (2 * l + 1) * R * S * D : nullptr);
+      w.rcross.sk.push_back(sc ? sc + 2 * l * R * S : nullptr);
+      w.rcross.sv.push_back(sc ? sc + (2 * l + 1) * R * S : nullptr);
+    }
+    w.rmask = ar.take<uint8_t>(R * S);
+  }
+  w.tmask = ar.take<uint8_t>(R * T * T);
+  w.out = ar.take<float>(R * T * D);
+  w.logits_bytes = score_logits_bytes(c.tgt_vocab, (long)(R * T));
+  w.logits = ar.take<float>(w.logits_bytes / 4);
+  return w;
+}
+
+size_t score_ws(const qtx_config& c, long B, long S, long L, long K, long nf) {
+  Arena ar;
+  carve_score(ar, c, B, S, L, K, nf);
+  return align_up(ar.used);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t qtx_score_workspace_size(const qtx_model* m, int32_t B, int32_t S, int32_t L,
+                                int32_t tgt_per_src, int32_t n_faults) {
+  if (!m || B <= 0 || S <= 0 || L < 2 || tgt_per_src < 1 || n_faults < 0) return 0;
+  return score_ws(m->cfg, B, S, L, tgt_per_src, n_faults);
+}
+
+int32_t qtx_score_targets(const qtx_model* m, const int64_t* src, const uint8_t* src_mask,
+                          int32_t B, int32_t S, const int64_t* tgt, int32_t L,
+                          int32_t tgt_per_src, int64_t pad, const qtx_fault* faults,
+                          int32_t n_faults, float* tok_logp, int32_t* rank, int64_t* top_ids,
+                          float* top_logp, void* ws, size_t ws_bytes, void* stream) {
+  if (!m || !src || !src_mask || !tgt || !tok_logp || !rank || !ws)
+    return fail(QTX_E_INVALID, "null argument");
+  if (!top_ids != !top_logp) return fail(QTX_E_INVALID, "top_ids and top_logp come as a pair");
+  const qtx_config& c = m->cfg;
+  const int K = tgt_per_src, T = L - 1;
+  if (B <= 0 || S <= 0 || S > 512 || S > c.max_len || L < 2 || T > 512 || T > c.max_len || K < 1)
+    return fail(QTX_E_INVALID, "bad shape B=%d S=%d L=%d tgt_per_src=%d", B, S, L, K);
+  if (c.tgt_vocab < 2) return fail(QTX_E_INVALID, "scoring needs tgt_vocab >= 2 (%d)", c.tgt_vocab);
+  if (n_faults < 0 || (n_faults > 0 && !faults))
+    return fail(QTX_E_INVALID, "n_faults %d without a fault array", n_faults);
+  const long Rl = (long)B * K;
+  if (Rl * T * c.d_model >= (1L << 30))
+    return fail(QTX_E_UNSUPPORTED, "target scoring: B * tgt_per_src * (L - 1) * d_model must be "
+                                   "below 2^30");
+  if (n_faults > 0) {
+    if (c.weight_bits != 8) return fail(QTX_E_UNSUPPORTED, "fault injection needs 8-bit weights");
+    if (K != 1) return fail(QTX_E_UNSUPPORTED, "fault trials need tgt_per_src == 1 (%d)", K);
+    for (int n = 0; n < n_faults; ++n) {
+      const qtx_fault* f = faults + n;
+      if (f->kind == QTX_FAULT_NONE) return fail(QTX_E_INVALID, "fault %d: kind NONE", n);
+      if (f->module == 0) RC(check_fault(m, f, 0, B, S, 0));
+      else if (f->module == 1) RC(check_fault(m, f, 1, B, T, S));
+      else return fail(QTX_E_INVALID, "fault %d: module %d", n, f->module);
+    }
+  }
+  if (ws_bytes < score_ws(c, B, S, L, K, n_faults))
+    return fail(QTX_E_WORKSPACE, "workspace too small");
+  dfault_forget(m, ws);
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar;
+  ar.base = (uint8_t*)ws; ar.cap = ws_bytes;
+  unsigned* cst = nullptr;
+  RC(call_status_begin(m, &cst, st));
+  ScoreWS w = carve_score(ar, c, B, S, L, K, n_faults);
+  w.enc.status = cst;
+  const int D = c.d_model, R = (int)Rl, Ms = B * S;
+  const long M = (long)R * T;
+  auto embed_src = [&]() -> int {
+    HIPCHK(launch_embed(src, S, B, S, nullptr, 0, m->src_lut, c.src_vocab, m->pe, c.max_len,
+                        w.enc.x, (long)S * D, st));
+    return QTX_OK;
+  };
+  // the golden encoder pass and cross K/V, once on the B sentences (greedy_prologue's)
+  RC(embed_src());
+  RC(encoder_run(m, w.enc.x, src_mask, B, S, w.memory, w.enc, st, nullptr));
+  RC(cross_kv(m, w.memory, Ms, w.cross, st));
+  const CrossKV* gx = &w.cross;
+  const uint8_t* rmask = src_mask;
+  if (K > 1) {   // row r reads the cross K/V and the source mask of sentence r / K
+    for (int l = 0; l < c.n_layers; ++l) {
+      HIPCHK(launch_beam_rep(w.cross.k8[l], w.rcross.k8[l], B, K, (long)S * D, st));
+      HIPCHK(launch_beam_rep(w.cross.v8[l], w.rcross.v8[l], B, K, (long)S * D, st));
+      HIPCHK(launch_beam_rep(w.cross.sk[l], w.rcross.sk[l], B, K, S * 4L, st));
+      HIPCHK(launch_beam_rep(w.cross.sv[l], w.rcross.sv[l], B, K, S * 4L, st));
+    }
+    HIPCHK(launch_beam_rep(src_mask, w.rmask, B, K, S, st));
+    gx = &w.rcross;
+    rmask = w.rmask;
+  }
+  long tm_bs = 0;
+  if (pad >= 0) {
+    HIPCHK(launch_std_mask(tgt, R, L, pad, w.tmask, st));
+    tm_bs = (long)T * T;
+  } else {
+    HIPCHK(launch_causal_mask(w.tmask, T, st));
+  }
+  for (int n = 0; n <= n_faults; ++n) {   // trial 0 golden, trial n: faults[n - 1]
+    const qtx_fault* f = n ? faults + n - 1 : nullptr;
+    const CrossKV* x = gx;
+    if (f && f->module == 0) {   // the encoder and the cross K/V again, into the trial's own buffers
+      RC(embed_src());
+      RC(encoder_run(m, w.enc.x, src_mask, B, S, w.fmemory, w.enc, st, f));
+      RC(cross_kv(m, w.fmemory, Ms, w.fcross, st));
+      x = &w.fcross;
+      f = nullptr;
+    } else if (f) {              // a memory K / V projection fault: its own cross copy
+      bool ckv_fault = false;
+      for (int l = 0; l < c.n_layers; ++l)
+        ckv_fault |= fault_for(f, 1, l, G_CKV, Ms, c).kind != FK_NONE;
+      if (ckv_fault) {
+        RC(cross_kv(m, w.memory, Ms, w.fcross, st, f));
+        x = &w.fcross;
+      }
+    }
+    HIPCHK(launch_embed(tgt, L, R, T, nullptr, 0, m->tgt_lut, c.tgt_vocab, m->pe, c.max_len,
+                        w.dec.x, (long)T * D, st));
+    RC(decoder_body(m, w.dec, *x, rmask, w.tmask, tm_bs, R, T, S, w.out, f, st));
+    const long o = (long)n * M;
+    RC(score_rows_run(m, w.out, M, tgt + 1, T, L, tok_logp + o, rank + o,
+                      top_ids ? top_ids + 2 * o : nullptr, top_logp ? top_logp + 2 * o : nullptr,
+                      w.logits, score_chunk(w.logits_bytes, c.tgt_vocab, M), st));
+  }
+  return QTX_OK;
+}
+
+int32_t qtx_score_logits(const float* logits, const int64_t* y, int32_t M, int32_t V,
+                         float* tok_logp, int32_t* rank, int64_t* top_ids, float* top_logp,
+                         void* stream) {
+  if (!logits || !y || !tok_logp || !rank) return fail(QTX_E_INVALID, "null argument");
+  if (!top_ids != !top_logp) return fail(QTX_E_INVALID, "top_ids and top_logp come as a pair");
+  if (V < 2) return fail(QTX_E_INVALID, "scoring needs V >= 2 (%d)", V);
+  if (M <= 0) return QTX_OK;
+  HIPCHK(launch_lsm_score(logits, M, V, y, 0, 1, 1, tok_logp, rank, top_ids, top_logp,
+                          (hipStream_t)stream));
+  return QTX_OK;
+}
+
+int32_t qtx_score_rows(const qtx_model* m, const float* x, int32_t M, const int64_t* y,
+                       float* tok_logp, int32_t* rank, int64_t* top_ids, float* top_logp,
+                       void* ws, size_t ws_bytes, void* stream) {
+  if (!m || !x || !y || !tok_logp || !rank || !ws) return fail(QTX_E_INVALID, "null argument");
+  if (!top_ids != !top_logp) return fail(QTX_E_INVALID, "top_ids and top_logp come as a pair");
+  const int V = m->cfg.tgt_vocab;
+  if (V < 2) return fail(QTX_E_INVALID, "scoring needs tgt_vocab >= 2 (%d)", V);
+  if (M <= 0) return QTX_OK;
+  if ((long)M * m->cfg.d_model >= (1L << 30))
+    return fail(QTX_E_UNSUPPORTED, "score rows: M * d_model must be below 2^30");
+  const int chunk = score_chunk(ws_bytes, V, M);
+  if (!chunk) return fail(QTX_E_WORKSPACE, "ws holds fewer than 16 rows of logits");
+  return score_rows_run(m, x, M, y, 1, 1, tok_logp, rank, top_ids, top_logp, (float*)ws, chunk,
+                        (hipStream_t)stream);
+}
+
+}  // extern "C"
+
 extern "C" {
 
 // ---- per-op entry points ---------------------------------------------------------------

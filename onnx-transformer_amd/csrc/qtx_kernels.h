@@ -322,6 +322,17 @@ hipError_t launch_logsoftmax_argmax(const float* logits, int M, int V, float* lo
 hipError_t launch_logsoftmax_top2(const float* logits, int M, int V, int64_t* ids, long ids_bs,
                                   const int* col_dev, int col_add, int64_t* top_ids,
                                   float* top_logp, long top_bs, hipStream_t st);
+// teacher-forced scoring (include/qtx.h, target scoring; no logp write).  Row i of logits
+// [M, V] is global row g = m0 + i: its label is y[(g / y_t) * y_l + g % y_t] (y_t = y_l = 1:
+// y[g]), its outputs entry g of tok_logp / rank and entry g of top_ids / top_logp [.., 2]
+// (both null: not written).  A non-finite row or a label outside [0, V): NaN, rank -1.  V >= 2.
+hipError_t launch_lsm_score(const float* logits, int M, int V, const int64_t* y, long m0, int y_t,
+                            int y_l, float* tok_logp, int* rank, int64_t* top_ids,
+                            float* top_logp, hipStream_t st);
+// make_std_mask (batch.py:25-30): tgt int64 [R, L] -> mask uint8 [R, L-1, L-1],
+// keep[r][i][j] = j <= i and tgt[r][j] != pad
+hipError_t launch_std_mask(const int64_t* tgt, int R, int L, int64_t pad, uint8_t* mask,
+                           hipStream_t st);
 hipError_t launch_pack_int4(const int8_t* q, int N, int K, uint8_t* packed, hipStream_t st);
 hipError_t launch_u8_from_any(const void* src, int elem_bytes, long n, uint8_t* dst,
                               hipStream_t st);

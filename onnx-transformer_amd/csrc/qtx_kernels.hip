@@ -9,6 +9,9 @@
 //   k_generator     fp32 x.W^T + b (sequential fma chain over k)     generator.py:14-15
 //   k_lsm_argmax    log_softmax + first-index argmax                 onnx_reference_inference.py:640-641
 //   k_lsm_top2      log_softmax + the two best (id, logp)            parallelized_inject_onnx_transformer.py:718-740
+//   k_lsm_score     log_softmax + a given label's logp, rank, top 2  generator.py:15 on
+//                                                                    encoder_decoder.py:19-23
+//   k_std_mask      the pad-aware causal target mask                 batch.py:25-30
 //
 // Every float step follows the canonical order of qtx_common.h / oracle/qtx_oracle.py.
 #include <cstdlib>
@@ -579,6 +582,89 @@ hipError_t launch_logsoftmax_top2(const float* logits, int M, int V, int64_t* id
   if (V < 2) return hipErrorInvalidValue;
   k_lsm_top2<<<dim3(M), dim3(64), 0, st>>>(logits, V, ids, ids_bs, col_dev, col_add, top_ids,
                                            top_logp, top_bs);
+  return hipGetLastError();
+}
+
+// =====================================================================================
+// k_lsm_score: k_lsm_top2's teacher-forced sibling (include/qtx.h: target scoring).  One wave
+// per logits row; the row's label is y[(g / y_t) * y_l + g % y_t] for the global row
+// g = m0 + blockIdx.x (y_t = y_l = 1: y[g]; the model-level call reads tgt[:, 1:] in place).
+// After row_lse every lane forms logp[y] from one broadcast load of x[y]; one more pass over
+// the row forms the top 2 and counts the entries that come before the label under "larger
+// logp, then smaller index" — its rank.  No [M, V] log-prob write.  A non-finite row or a
+// label outside [0, V): tok_logp NaN, rank -1 (the label is clamped for the load: nothing
+// outside the row is read); the selects are wave-uniform.  V >= 2.
+// =====================================================================================
+__global__ __launch_bounds__(64) void k_lsm_score(const float* logits, int V, const int64_t* y,
+                                                  long m0, int y_t, int y_l, float* tok_logp,
+                                                  int* rank, int64_t* top_ids, float* top_logp) {
+  const int lane = threadIdx.x;
+  const long g = m0 + blockIdx.x;
+  const float* x = logits + (long)blockIdx.x * V;
+  float mx, lse;
+  bool bad;
+  row_lse(x, V, lane, mx, lse, bad);
+  const long yl = y[(g / y_t) * y_l + g % y_t];
+  const bool inside = yl >= 0 && yl < V;
+  const int yi = inside ? (int)yl : 0;
+  const float ly = (x[yi] - mx) - lse;                         // the same load in every lane
+  Top2 top;
+  int cnt = 0;
+  if (bad) {                                                   // wave-uniform
+    top.i1 = 0; top.i2 = 1;
+    top.v1 = top.v2 = __builtin_nanf("");
+  } else {
+#pragma unroll 4
+    for (int v = lane; v < V; v += 64) {
+      const float lp = (x[v] - mx) - lse;
+      top.add(lp, v);
+      cnt += Top2::before(lp, v, ly, yi) ? 1 : 0;
+    }
+    wave_top2(top);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) cnt += __shfl_xor(cnt, off, 64);
+  }
+  if (lane == 0) {
+    const bool ok = inside && !bad;
+    tok_logp[g] = ok ? ly : __builtin_nanf("");
+    rank[g] = ok ? cnt : -1;
+    if (top_ids) {
+      top_ids[2 * g] = top.i1; top_ids[2 * g + 1] = top.i2;
+      top_logp[2 * g] = top.v1; top_logp[2 * g + 1] = top.v2;
+    }
+  }
+}
+
+hipError_t launch_lsm_score(const float* logits, int M, int V, const int64_t* y, long m0, int y_t,
+                            int y_l, float* tok_logp, int* rank, int64_t* top_ids,
+                            float* top_logp, hipStream_t st) {
+  if (M <= 0) return hipSuccess;
+  if (V < 2 || y_t < 1 || y_l < 1 || !top_ids != !top_logp) return hipErrorInvalidValue;
+  k_lsm_score<<<dim3(M), dim3(64), 0, st>>>(logits, V, y, m0, y_t, y_l, tok_logp, rank, top_ids,
+                                            top_logp);
+  return hipGetLastError();
+}
+
+// =====================================================================================
+// k_std_mask: the reference's make_std_mask (batch.py:25-30) for teacher-forced targets:
+// tgt int64 [R, L] -> mask uint8 [R, T, T], T = L - 1, keep[r][i][j] = j <= i and
+// tgt[r][j] != pad (the decoder's input is tgt[:, :T]).
+// =====================================================================================
+__global__ __launch_bounds__(256) void k_std_mask(const int64_t* tgt, int R, int L, int64_t pad,
+                                                  uint8_t* mask) {
+  const int T = L - 1;
+  const long n = (long)blockIdx.x * 256 + threadIdx.x;
+  if (n >= (long)R * T * T) return;
+  const int j = (int)(n % T), i = (int)((n / T) % T);
+  const long r = n / ((long)T * T);
+  mask[n] = (j <= i && tgt[r * L + j] != pad) ? 1 : 0;
+}
+
+hipError_t launch_std_mask(const int64_t* tgt, int R, int L, int64_t pad, uint8_t* mask,
+                           hipStream_t st) {
+  if (R <= 0 || L < 2) return hipSuccess;
+  const long n = (long)R * (L - 1) * (L - 1);
+  k_std_mask<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(tgt, R, L, pad, mask);
   return hipGetLastError();
 }
 

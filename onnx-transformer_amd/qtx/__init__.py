@@ -7,6 +7,8 @@ Public surface mirrors the reference's entry points:
   greedy_decode(model, src, src_mask, max_len, start_symbol)
   greedy_decode(..., return_scores=True) -> (ys, Scores)   ~ the campaign's torch.topk(prob, 2)
   decode_fault_sweep(model, src, src_mask, max_len, start_symbol, trials)   ~ a campaign's trials
+  score_targets(model, src, src_mask, tgt) -> TargetScores   ~ EncoderDecoder.forward on a given
+                                                               target + log_softmax
 """
 from .weights import (BOS, DEFAULT_SEED, EOS, PAD, UNK, ModelConfig, load_checkpoint,
                       positional_table, synthetic_state_dict, tensor_order)
@@ -15,7 +17,8 @@ __all__ = ["BOS", "EOS", "PAD", "UNK", "DEFAULT_SEED", "ModelConfig", "load_chec
            "positional_table", "synthetic_state_dict", "tensor_order", "QtxModel",
            "InferenceSession", "run_module", "set_default_model", "greedy_decode",
            "greedy_decode_fault", "decode_fault_sweep", "plan_sweep", "SweepStats", "Scores",
-           "FaultStepRecord", "make_src_mask", "lib"]
+           "FaultStepRecord", "make_src_mask", "score_targets", "rescore_beam", "TargetScores",
+           "lib"]
 
 
 def __getattr__(name):
@@ -27,7 +30,8 @@ def __getattr__(name):
         from . import session
         return getattr(session, name)
     if name in ("greedy_decode", "greedy_decode_fault", "decode_fault_sweep", "plan_sweep",
-                "SweepStats", "Scores", "FaultStepRecord", "make_src_mask"):
+                "SweepStats", "Scores", "FaultStepRecord", "make_src_mask", "score_targets",
+                "rescore_beam", "TargetScores"):
         from . import decode
         return getattr(decode, name)
     if name == "lib":

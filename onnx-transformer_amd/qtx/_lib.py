@@ -109,6 +109,11 @@ SIGNATURES = {
     "qtx_beam_select": (I32, [P, P, I32, I32, I64, I64, I32, P, P, P, P, P, P, P, P, P]),
     "qtx_beam_reorder": (I32, [P, P, P, P, I32, I32, I32, I32, I64, I64, I64, I32, P, P, P]),
     "qtx_generator_top2": (I32, [P, P, I32, P, P, P, SZ, P]),
+    "qtx_score_workspace_size": (SZ, [P, I32, I32, I32, I32, I32]),
+    "qtx_score_targets": (I32, [P, P, P, I32, I32, P, I32, I32, I64, FP, I32, P, P, P, P, P, SZ,
+                                P]),
+    "qtx_score_logits": (I32, [P, P, I32, I32, P, P, P, P, P]),
+    "qtx_score_rows": (I32, [P, P, I32, P, P, P, P, P, P, SZ, P]),
     "qtx_decode_top2_embed": (I32, [P, P, I32, P, I64, P, P, P, P, P]),
     "qtx_decode_generator": (I32, [P, P, I32, P, P, P]),
     "qtx_debug_nop": (I32, [P]),

@@ -24,6 +24,7 @@ order is the file order, so a run is reproducible.
 """
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass
 
@@ -115,6 +116,43 @@ def score(ids, tgt, vocab_tgt: Vocab) -> EvalResult:
             sb.append(None)
     return EvalResult(bleu.corpus_bleu(refs, hyps), sb, hyps, [r[0] for r in refs],
                       np.asarray(ids))
+
+
+@dataclass
+class PerplexityResult:
+    nll: float                  # -sum of the label log-probabilities (float64, math.fsum), pads excluded
+    n_tokens: int               # labels counted
+    ppl: float                  # exp(nll / n_tokens)
+    token_accuracy: float       # share of labels that are the model's first choice (rank 0)
+    sentence_logp: np.ndarray   # float64 [N] per sentence
+
+
+def perplexity(model, pairs, vocab_src: Vocab, vocab_tgt: Vocab, batch_size: int = 32,
+               max_padding: int = 128, score=None) -> PerplexityResult:
+    """Teacher-forced evaluation of ``pairs`` in file order, batched as evaluate() does: the
+    reference targets' negative log-likelihood, perplexity and token accuracy.  Each batch's
+    targets are trimmed to its longest sentence (exact: positions are causal, and pad labels
+    are not counted).  ``score(src, src_mask, tgt) -> TargetScores`` defaults to the qtx GPU
+    path (qtx.decode.score_targets)."""
+    if score is None:
+        from .decode import score_targets
+
+        def score(s, m, t):
+            return score_targets(model, s, m, t, pad=PAD, return_top2=False)
+    src, tgt = collate(pairs, vocab_src, vocab_tgt, max_padding)
+    n_tok, n_hit, sent = 0, 0, []
+    for b0 in range(0, len(pairs), batch_size):
+        s, t = src[b0:b0 + batch_size], tgt[b0:b0 + batch_size]
+        t = t[:, :max(2, int((t != PAD).sum(-1).max()))]
+        ts = score(s, (s != PAD)[:, None, :], t)
+        sl = np.asarray(ts.sentence_logp, np.float64)
+        sent.append(sl)
+        n_tok += int(np.asarray(ts.n_tokens).sum())
+        n_hit += int(np.asarray(ts.hits).sum())
+    sent = np.concatenate(sent) if sent else np.zeros((0,), np.float64)
+    nll = -math.fsum(sent)      # correctly rounded: independent of the batching
+    return PerplexityResult(nll, n_tok, float(np.exp(nll / n_tok)) if n_tok else float("nan"),
+                            n_hit / n_tok if n_tok else float("nan"), sent)
 
 
 def beam_decoder(model, **beam_kwargs):

@@ -123,6 +123,110 @@ def beam_decode(model: QtxModel, src, src_mask, max_len: int, start_symbol: int 
     return BeamResult(*out, steps_run=steps)
 
 
+@dataclasses.dataclass
+class TargetScores:
+    """score_targets' result (numpy or torch, like the src it came from): per target row r and
+    position t the model's opinion of the label tgt[r, t+1] given tgt[r, :t+1] (include/qtx.h,
+    target scoring).  ``tok_logp`` float32 and ``rank`` int32 [R, T] (rank 0: the label is the
+    model's first choice; -1 and NaN for a non-finite row), ``top_ids`` int64 and ``top_logp``
+    float32 [R, T, 2] (None without return_top2), ``labels`` int64 [R, T] = tgt[:, 1:].  With
+    fault trials every array but ``labels`` has a leading axis of 1 + len(faults), index 0
+    golden.  Positions whose label is ``pad`` are computed like any other; ``mask`` excludes
+    them (pad < 0: nothing is excluded)."""
+    tok_logp: object
+    rank: object
+    top_ids: object
+    top_logp: object
+    labels: object
+    pad: int = PAD
+
+    @property
+    def mask(self):
+        """labels != pad, [R, T] bool."""
+        return self.labels != self.pad
+
+    @property
+    def n_tokens(self):
+        """Labels under the mask per row, [R]."""
+        return self.mask.sum(-1)
+
+    @property
+    def sentence_logp(self):
+        """The float64 sum of tok_logp under the mask, [.., R]: correctly rounded (math.fsum),
+        so it depends neither on the order of the terms nor on how far the rows are padded."""
+        import math
+        is_np = isinstance(self.tok_logp, np.ndarray)
+        lp = np.asarray(self.tok_logp if is_np else self.tok_logp.cpu().numpy(), np.float64)
+        m = np.broadcast_to(np.asarray(self.mask if is_np else self.mask.cpu().numpy()), lp.shape)
+        flat = [math.fsum(r[k]) for r, k in zip(lp.reshape(-1, lp.shape[-1]),
+                                                m.reshape(-1, lp.shape[-1]))]
+        out = np.asarray(flat, np.float64).reshape(lp.shape[:-1])
+        if is_np:
+            return out
+        import torch
+        return torch.from_numpy(out).to(self.tok_logp.device)
+
+    @property
+    def hits(self):
+        """rank == 0 under the mask, [.., R, T] bool: the label is what greedy would pick."""
+        return (self.rank == 0) & self.mask
+
+
+def score_targets(model: QtxModel, src, src_mask, tgt, pad: int = PAD, tgt_per_src: int = 1,
+                  faults=None, return_top2: bool = True) -> TargetScores:
+    """Teacher-forced scoring (include/qtx.h, target scoring; the reference's
+    EncoderDecoder.forward on Batch.tgt / tgt_y, encoder_decoder.py:19-23, batch.py:17-30):
+    src int64 [B,S] (numpy or torch), src_mask [B,1,S] bool, tgt int64 [B * tgt_per_src, L]
+    (row r a target of sentence r // tgt_per_src) -> TargetScores of the L - 1 labels
+    tgt[:, 1:].  One library call: the encoder once on the B sentences, one decoder pass over
+    all positions, no [.., V] log-probabilities materialised.  faults: a list of
+    qtx.fault.Fault, each a trial of its own on the same call (arrays then [1 + len, R, T],
+    index 0 golden; 8-bit weights and tgt_per_src == 1).  A label outside the vocabulary
+    raises ValueError."""
+    import torch
+    was_numpy = isinstance(src, np.ndarray)
+    src_t = torch.from_numpy(np.ascontiguousarray(src)) if was_numpy else src
+    tgt_t = torch.from_numpy(np.ascontiguousarray(tgt)) if isinstance(tgt, np.ndarray) else tgt
+    B, S = src_t.shape
+    labels = tgt_t[:, 1:]
+    if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= model.cfg.tgt_vocab):
+        raise ValueError(f"a label lies outside the vocabulary [0, {model.cfg.tgt_vocab})")
+    srcd = src_t.to(model.device, torch.int64).contiguous()
+    tgtd = tgt_t.to(model.device, torch.int64).contiguous()
+    md = to_u8_mask(src_mask, model.device).reshape(B, S)
+    out = model.score(srcd, md, tgtd, pad=pad, tgt_per_src=tgt_per_src, faults=faults,
+                      return_top2=return_top2)
+    model.check()
+    to_host = (lambda t: t.cpu().numpy()) if was_numpy else (lambda t: t.to(src_t.device))
+    out = [None if t is None else to_host(t if faults is not None else t[0]) for t in out]
+    return TargetScores(*out, labels=to_host(labels.to(torch.int64).contiguous()), pad=int(pad))
+
+
+def accumulate_logp(tok_logp, lengths):
+    """Per row the float32 sequential sum acc = fl32(acc + tok_logp[t]) over t < lengths[r]:
+    the accumulation of the beam search's score (include/qtx.h, beam search rule 3)."""
+    lp = np.asarray(tok_logp, np.float32)
+    n = np.asarray(lengths)
+    acc = np.zeros(lp.shape[:-1], np.float32)
+    for t in range(lp.shape[-1]):
+        acc = np.where(t < n, (acc + lp[..., t]).astype(np.float32), acc)
+    return acc
+
+
+def rescore_beam(model: QtxModel, src, src_mask, beam_result: BeamResult, pad: int = PAD):
+    """Score a beam search's own hypotheses teacher-forced (score_targets on ``hyp_ids`` with
+    tgt_per_src = beam) and add each one's label log-probabilities up as the search did:
+    sequentially in float32 over t < hyp_len.  Returns float32 [B, beam] (numpy), equal to
+    ``hyp_score`` bit for bit wherever the scores are finite: the full-prefix pass computes
+    the cached steps' log-probabilities exactly."""
+    to_np = lambda a: a if isinstance(a, np.ndarray) else a.cpu().numpy()
+    hyp_ids, hyp_len = to_np(beam_result.hyp_ids), to_np(beam_result.hyp_len)
+    B, K, L = hyp_ids.shape
+    ts = score_targets(model, to_np(src), to_np(src_mask), hyp_ids.reshape(B * K, L), pad=pad,
+                       tgt_per_src=K, return_top2=False)
+    return accumulate_logp(ts.tok_logp, hyp_len.reshape(B * K)).reshape(B, K)
+
+
 def greedy_decode_fault(model: QtxModel, src, src_mask, max_len: int, start_symbol: int = 0,
                         fault=None, target_inference_number: int = 1,
                         return_scores: bool = False, kv_cache: bool = False):

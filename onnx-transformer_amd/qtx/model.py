@@ -203,6 +203,38 @@ class QtxModel:
         return hyp_ids, hyp_score, hyp_len, int(steps.value)
 
     @_on_device
+    def score(self, src, src_mask_u8, tgt, pad: int = PAD, tgt_per_src: int = 1, faults=None,
+              return_top2: bool = True):
+        """Teacher-forced scoring of given targets (qtx_score_targets).  src int64 [B,S],
+        src_mask [B,S] u8, tgt int64 [R,L] with R = B * tgt_per_src (row r a target of sentence
+        r // tgt_per_src) -> (tok_logp f32, rank int32 [N+1,R,L-1], top_ids int64, top_logp f32
+        [N+1,R,L-1,2] or None, None) on the device: entry t scores tgt[:, t+1] given
+        tgt[:, :t+1].  faults: a list of N qtx.fault.Fault (trial 0 is fault-free, trial n
+        applies faults[n-1] alone); pad < 0: the causal target mask alone."""
+        torch = _torch()
+        B, S = src.shape
+        R, L = tgt.shape
+        K = int(tgt_per_src)
+        if K < 1 or R != B * K:
+            raise ValueError(f"tgt has {R} rows for {B} sentences x tgt_per_src {K}")
+        faults = list(faults or [])
+        N = len(faults)
+        T = max(L - 1, 0)
+        tok_logp = torch.empty((N + 1, R, T), dtype=torch.float32, device=self.device)
+        rank = torch.empty((N + 1, R, T), dtype=torch.int32, device=self.device)
+        top_ids = top_logp = None
+        if return_top2:
+            top_ids = torch.empty((N + 1, R, T, 2), dtype=torch.int64, device=self.device)
+            top_logp = torch.empty((N + 1, R, T, 2), dtype=torch.float32, device=self.device)
+        farr = (_lib.Fault * N)(*[f.to_c() for f in faults]) if N else None
+        nb = _lib.lib().qtx_score_workspace_size(self.handle, B, S, L, K, N)
+        ws = self.workspace(nb)
+        _lib.call("qtx_score_targets", self.handle, _ptr(src), _ptr(src_mask_u8), B, S, _ptr(tgt),
+                  L, K, int(pad), farr, N, _ptr(tok_logp), _ptr(rank), _ptr(top_ids),
+                  _ptr(top_logp), _ptr(ws), ws.numel(), _stream(self.device))
+        return tok_logp, rank, top_ids, top_logp
+
+    @_on_device
     def dfault_workspace(self, B: int, S: int, max_len: int):
         """A workspace of its own for greedy_dfault / greedy_dfault_resume (uint8 device
         tensor): a resume reads what the last call left in it, so it is not the shared
