@@ -681,6 +681,13 @@ int32_t qtx_decode_generator(const qtx_model* m, const float* x, int32_t M, floa
  * counterpart). */
 int32_t qtx_debug_nop(void* stream);
 
+/* The model's cache of captured decode-step graphs: *entries = the entries it holds now (at
+ * most 16; a capture that would pass that clears the cache first), *captures = the graphs
+ * instantiated since the model was created, one per executable graph (a capture of G separate
+ * sub-batch graphs counts G).  Takes the model's lock (test / measurement only, no
+ * reference counterpart). */
+int32_t qtx_debug_graph_stats(const qtx_model* m, int32_t* entries, int64_t* captures);
+
 /* Re-read the library's environment switches (csrc/qtx_knobs.h), which are otherwise read
  * once: the path switches the tests use to force the library's alternative code paths
  * (QTX_NO_GRAPH, QTX_UNFUSED, QTX_DECODE_GROUPS, QTX_NO_WSX, ...) and the hooks of the FFN1

@@ -18,6 +18,7 @@
 #include "qtx_kernels.h"
 #include "qtx_knobs.h"
 #include "qtx_carve.h"   // Arena, Scratch, CrossKV, GreedyWS, BeamWS and their carving
+#include "qtx_stepgraph.h"   // StepGraphs: the decode graphs' capture, cache and replay
 
 using namespace qtx;
 
@@ -64,6 +65,10 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 }  // namespace
 
+int qtx::stepgraph_hip_error(const char* what, hipError_t e) {
+  return fail(QTX_E_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+
 // One quantized linear: int8 q [N,K] (or packed int4 [N,K/2]), per-channel scale, bias.
 struct QLin {
   int8_t* q = nullptr;
@@ -91,26 +96,6 @@ struct DecLayer {
   const float* ln[3][2];
 };
 
-// The captured decode graphs depend on the shapes and the workspace only: the caller's
-// ids and src_mask are staged through workspace buffers around each replay, so callers
-// that allocate fresh id/mask tensors per call still hit the cache.
-struct GraphKey {
-  int B, S, L, G;
-  const void* ws;
-  std::string variant;   // the QTX_* experiment switches the captured step depends on
-  bool operator<(const GraphKey& o) const {
-    return std::tie(B, S, L, G, ws, variant) < std::tie(o.B, o.S, o.L, o.G, o.ws, o.variant);
-  }
-};
-struct GraphEntry {
-  std::vector<hipGraphExec_t> execs;   // one graph per sub-batch
-  hipEvent_t done = nullptr;           // recorded after the entry's last replay
-};
-
-// The fused decode runs the batch as up to QTX_MAX_GROUPS independent sub-batches, each a
-// graph on its own stream (qtx_greedy_decode).
-constexpr int QTX_MAX_GROUPS = 4;
-
 struct qtx_model {
   qtx_config cfg;
   std::vector<EncLayer> enc;
@@ -125,11 +110,9 @@ struct qtx_model {
   QLin ckv_all;
   void* mem = nullptr;
   size_t bytes = 0;
-  // decode-step graphs, keyed by shape and the buffers baked into them
+  // guards sg, dfault and the encoder's second stream
   std::mutex mu;
-  hipStream_t gstream[QTX_MAX_GROUPS] = {};
-  hipEvent_t ev_in = nullptr, ev_out[QTX_MAX_GROUPS] = {};
-  std::map<GraphKey, GraphEntry> graphs;
+  StepGraphs sg;   // the decode-step graphs with their streams and events (qtx_stepgraph.h)
   // validity headers of the decoder-fault decode's workspaces, by workspace pointer (guarded
   // by mu; include/qtx.h qtx_greedy_dfault_resume)
   struct DfaultHdr {
@@ -151,17 +134,6 @@ struct qtx_model {
   std::vector<bool> slot_used;     // a live thread holds the slot (qtx_api.hip CallStatus)
   std::vector<bool> slot_had_owner;  // a thread held the slot before (its kernels may still
                                      // be in flight on that thread's streams)
-  // an exec may still be running on a caller's stream: wait for its last replay first
-  void clear_graphs() {
-    for (auto& kv : graphs) {
-      if (kv.second.done) {
-        (void)hipEventSynchronize(kv.second.done);
-        (void)hipEventDestroy(kv.second.done);
-      }
-      for (hipGraphExec_t e : kv.second.execs) (void)hipGraphExecDestroy(e);
-    }
-    graphs.clear();
-  }
 };
 
 namespace {
@@ -319,6 +291,17 @@ int call_status_begin(const qtx_model* mc, unsigned** word, hipStream_t st) {
 int enc_tensor_base(const qtx_config& c, int L) { return 12 * L; }
 int dec_tensor_base(const qtx_config& c, int L) { return 12 * c.n_layers + 20 * L; }
 int norm_tensor_base(const qtx_config& c) { return 32 * c.n_layers; }
+
+// The shapes every decode and the target scoring refuse: B sentences of S source tokens and
+// up to T target positions.
+bool bad_decode_shape(const qtx_config& c, int B, int S, int T) {
+  return B <= 0 || S <= 0 || S > 512 || T < 1 || T > 512 || T > c.max_len || S > c.max_len;
+}
+int check_decode_shape(const qtx_config& c, int B, int S, int max_len) {
+  if (bad_decode_shape(c, B, S, max_len))
+    return fail(QTX_E_INVALID, "bad shape B=%d S=%d max_len=%d", B, S, max_len);
+  return QTX_OK;
+}
 
 int check_cfg(const qtx_config* c) {
   if (!c) return fail(QTX_E_INVALID, "null config");
@@ -560,17 +543,10 @@ int32_t qtx_model_destroy(qtx_model* m) {
     std::lock_guard<std::mutex> lk(g_live_mu);   // no thread exit returns a slot to it now
     g_live.erase(m->serial);
   }
-  for (hipStream_t s : m->gstream)
-    if (s) (void)hipStreamSynchronize(s);
-  m->clear_graphs();
-  if (m->ev_in) (void)hipEventDestroy(m->ev_in);
+  m->sg.destroy();
   for (hipEvent_t e : {m->ev_fork, m->ev_lag, m->ev_join})
     if (e) (void)hipEventDestroy(e);
   if (m->estream) (void)hipStreamDestroy(m->estream);
-  for (int i = 0; i < QTX_MAX_GROUPS; ++i) {
-    if (m->ev_out[i]) (void)hipEventDestroy(m->ev_out[i]);
-    if (m->gstream[i]) (void)hipStreamDestroy(m->gstream[i]);
-  }
   if (m->mem) (void)hipFree(m->mem);
   delete m;
   return QTX_OK;
@@ -1707,9 +1683,7 @@ static int32_t greedy_decode(const qtx_model* m, const int64_t* src, const uint8
       (scored && max_len > 1 && (!top_ids || !top_logp)))   // (max_len 1: no step, no entry)
     return fail(QTX_E_INVALID, "null argument");
   const qtx_config& c = m->cfg;
-  if (B <= 0 || S <= 0 || S > 512 || max_len < 1 || max_len > 512 || max_len > c.max_len ||
-      S > c.max_len)
-    return fail(QTX_E_INVALID, "bad shape B=%d S=%d max_len=%d", B, S, max_len);
+  RC(check_decode_shape(c, B, S, max_len));
   if (scored && c.tgt_vocab < 2)
     return fail(QTX_E_INVALID, "scored decode needs tgt_vocab >= 2 (%d)", c.tgt_vocab);
   if (scored && knobs().dbg_tail)
@@ -1792,31 +1766,44 @@ bool greedy_fused(const qtx_config& c, int S, int max_len) {
   return S <= 128 && max_len <= 128 && fused_step_ok(c) && !knobs().unfused;
 }
 
-// What precedes the steps: the encoder, the cross K/V, ids[:, 0] and the step counters.
+// The encode step of every decode, on the B sentences: memory = encode(src_embed(src), mask),
+// the cross K/V of every layer into x and, for the fused step (cvg non-null), the cross
+// values in k_dec_attn's 4-key groups.
+// (captured into a hipGraph with the steps' replay — QTX_PRE_GRAPH in round 3 — it
+// measured no faster: 14.34 vs 14.31 ms per B = 32 decode; the host's enqueue of these
+// launches runs ahead of the GPU)
+int encode_src(const qtx_model* m, GreedyWS& g, const int64_t* src, const uint8_t* mask, int B,
+               int S, CrossKV& x, int8_t* cvg, const qtx_fault* f, hipStream_t st) {
+  const qtx_config& c = m->cfg;
+  const long D = c.d_model;
+  HIPCHK(launch_embed(src, S, B, S, nullptr, 0, m->src_lut, c.src_vocab, m->pe, c.max_len,
+                      g.enc.x, S * D, st));
+  RC(encoder_run(m, g.enc.x, mask, B, S, g.memory, g.enc, st, f));
+  RC(cross_kv(m, g.memory, B * S, x, st));
+  if (cvg) {
+    const long v_ls = c.n_layers > 1 ? (long)(x.v8[1] - x.v8[0]) : 0;
+    HIPCHK(launch_vgroup4(x.v8[0], v_ls, c.n_layers, B, S, cvg, (long)B * ((S + 3) & ~3) * D, st));
+  }
+  return QTX_OK;
+}
+
+// What precedes the steps: the encode step in place, ids[:, 0] and the step counters.
 int greedy_prologue(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S,
                     int max_len, int64_t start, const qtx_fault* f, bool fused, hipStream_t st) {
-  const qtx_config& c = m->cfg;
-  const int D = c.d_model;
-  const uint8_t* src_mask = g.mask;
-  int64_t* ids = g.ids;
-  // encoder: memory = encode(src_embed(src), src_mask); the cross K/V of every layer
-  // (captured into a hipGraph with the steps' replay — QTX_PRE_GRAPH in round 3 — it
-  // measured no faster: 14.34 vs 14.31 ms per B = 32 decode; the host's enqueue of these
-  // launches runs ahead of the GPU)
-  HIPCHK(launch_embed(src, S, B, S, nullptr, 0, m->src_lut, c.src_vocab, m->pe, c.max_len,
-                      g.enc.x, (long)S * D, st));
-  RC(encoder_run(m, g.enc.x, src_mask, B, S, g.memory, g.enc, st, f));
-  RC(cross_kv(m, g.memory, B * S, g.cross, st));
-  if (fused) {   // the cross values of every layer in k_dec_attn's 4-key groups
-    const long v_ls = g.cross.v8.size() > 1 ? (long)(g.cross.v8[1] - g.cross.v8[0]) : 0;
-    HIPCHK(launch_vgroup4(g.cross.v8[0], v_ls, c.n_layers, B, S, g.cvg[0],
-                          (long)B * ((S + 3) & ~3) * D, st));
-  }
-
+  RC(encode_src(m, g, src, g.mask, B, S, g.cross, fused ? g.cvg[0] : nullptr, f, st));
   // ids[:, 0] = start ; step[0] = position 0, step[1] = arrival counter
-  HIPCHK(launch_fill_col(ids, max_len, B, start, st));
+  HIPCHK(launch_fill_col(g.ids, max_len, B, start, st));
   HIPCHK(launch_zero(g.step, 16, st));
   return QTX_OK;
+}
+
+// The fused steps of a request through the model's step-graph runner, serialised per model
+// with the model's device current (the runner creates streams and events).
+int run_steps(const qtx_model* m, const StepRequest& rq, hipStream_t st) {
+  qtx_model* mm = const_cast<qtx_model*>(m);
+  std::lock_guard<std::mutex> lock(mm->mu);
+  DeviceGuard dg(mm->device);
+  return mm->sg.run(rq, st);
 }
 
 int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S, int max_len,
@@ -1841,149 +1828,27 @@ int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S
     HIPCHK(launch_embed(ids + (long)gr.b0(i) * max_len, max_len, gr.rows(i, B), 1, gv[i].step,
                         0, m->tgt_lut, c.tgt_vocab, m->pe, c.max_len, gv[i].dec.x, D, st));
   }
-  auto step_fn = [&](int i, hipStream_t s, int t) {
-    return greedy_step_fused(m, gv[i], gr.rows(i, B), S, max_len, ids + (long)gr.b0(i) * max_len,
-                             src_mask + (long)gr.b0(i) * S, s, t);
-  };
-  // One decode step per sub-batch captured once per (shape, buffers) as a hipGraph on its
-  // own stream and replayed max_len-1 times there; the streams fork from and join back
-  // into the caller's stream.
-  qtx_model* mm = const_cast<qtx_model*>(m);
-  std::lock_guard<std::mutex> lock(mm->mu);
-  DeviceGuard dg(mm->device);
-  if (!mm->ev_in) HIPCHK(hipEventCreateWithFlags(&mm->ev_in, hipEventDisableTiming));
-  for (int i = 0; i < gr.G; ++i)
-    if (!mm->gstream[i]) {
-      HIPCHK(hipStreamCreateWithFlags(&mm->gstream[i], hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&mm->ev_out[i], hipEventDisableTiming));
-    }
-  if (knobs().no_graph) {     // eager launches (QTX_NO_GRAPH); sub-batches on their streams
-    const bool fk = gr.G > 1;
-    if (fk) {
-      HIPCHK(hipEventRecord(mm->ev_in, st));
-      for (int i = 0; i < gr.G; ++i) HIPCHK(hipStreamWaitEvent(mm->gstream[i], mm->ev_in, 0));
-    }
-    for (int t = 0; t + 1 < max_len; ++t)
-      for (int i = 0; i < gr.G; ++i) RC(step_fn(i, fk ? mm->gstream[i] : st, t));
-    if (fk)
-      for (int i = 0; i < gr.G; ++i) {
-        HIPCHK(hipEventRecord(mm->ev_out[i], mm->gstream[i]));
-        HIPCHK(hipStreamWaitEvent(st, mm->ev_out[i], 0));
-      }
-    return QTX_OK;
-  }
+  if (max_len <= 1) return QTX_OK;
   // steps per graph: the whole decode in one graph by default (one graph launch); must
   // divide max_len-1 (the step position is read from device memory, so replays chain)
   int per_graph = max_len - 1;
   if (const int v = knobs().graph_steps; v > 0 && (max_len - 1) % v == 0) per_graph = v;
-  if (max_len <= 1) return QTX_OK;
+  StepRequest rq;
+  rq.key.rows = B; rq.key.S = S; rq.key.max_len = max_len;
+  rq.key.groups = gr.G;
+  rq.key.anchor = g.gsteps;
+  rq.key.form = g.top_ids ? StepForm::Scored : StepForm::Plain;   // the scored step: its own entry
   // a graph of the whole decode is replayed once per decode from position 0: each captured
   // step knows its position (a shorter graph replays at several)
-  const bool known = per_graph == max_len - 1;
-  const bool joint = gr.G > 1 && knobs().group_graph;
-  // the switches a captured step depends on are part of its key (knobs can be reloaded)
-  const Knobs& kn = knobs();
-  // (every switch: the key carries the knob generation, bumped by each reload — ADVICE r04:
-  // QTX_SKINNY_WIDE, QTX_RB_*, ... pick launch shapes inside the captured step too)
-  const std::string variant = std::to_string(knobs_generation()) + ":" + std::to_string(kn.split_ln) +
-                              std::to_string(kn.ffn_qkernel) + std::to_string(kn.group_graph) +
-                              std::to_string(kn.device_step) +
-                              (g.top_ids ? "s" : "");   // the scored step: an entry of its own
-  const GraphKey key{B, S, max_len, gr.G * 1000 + per_graph, g.gsteps, variant};
-  auto it = mm->graphs.find(key);
-  if (it == mm->graphs.end()) {
-    if (mm->graphs.size() >= 16) mm->clear_graphs();
-    std::vector<hipGraphExec_t> execs;
-    auto drop = [&] {
-      for (hipGraphExec_t e : execs) (void)hipGraphExecDestroy(e);
-    };
-    // QTX_GROUP_GRAPH (experiment): the G sub-batches as G independent branches of ONE graph
-    // (forked and joined inside the capture), launched on the caller's stream
-    if (joint) {
-      hipGraph_t graph = nullptr;
-      hipStream_t s0 = mm->gstream[0];
-      HIPCHK(hipStreamBeginCapture(s0, hipStreamCaptureModeThreadLocal));
-      int rc = QTX_OK;
-      hipError_t e = hipEventRecord(mm->ev_in, s0);
-      for (int i = 1; i < gr.G && e == hipSuccess; ++i) e = hipStreamWaitEvent(mm->gstream[i], mm->ev_in, 0);
-      for (int t = 0; t < per_graph && rc == QTX_OK && e == hipSuccess; ++t)
-        for (int i = 0; i < gr.G && rc == QTX_OK; ++i) rc = step_fn(i, mm->gstream[i], known ? t : -1);
-      for (int i = 1; i < gr.G && e == hipSuccess; ++i) {
-        e = hipEventRecord(mm->ev_out[i], mm->gstream[i]);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s0, mm->ev_out[i], 0);
-      }
-      const hipError_t e2 = hipStreamEndCapture(s0, &graph);
-      if (rc != QTX_OK || e != hipSuccess || e2 != hipSuccess) {
-        if (graph) (void)hipGraphDestroy(graph);
-        if (rc != QTX_OK) return rc;
-        HIPCHK(e != hipSuccess ? e : e2);
-      }
-      hipGraphExec_t exec = nullptr;
-      e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      HIPCHK(e);
-      execs.push_back(exec);
-    }
-    for (int i = 0; i < (joint ? 0 : gr.G); ++i) {
-      hipGraph_t graph = nullptr;
-      hipError_t e = hipStreamBeginCapture(mm->gstream[i], hipStreamCaptureModeThreadLocal);
-      if (e != hipSuccess) { drop(); HIPCHK(e); }
-      int rc = QTX_OK;
-      for (int t = 0; t < per_graph && rc == QTX_OK; ++t) rc = step_fn(i, mm->gstream[i], known ? t : -1);
-      e = hipStreamEndCapture(mm->gstream[i], &graph);
-      if (rc != QTX_OK || e != hipSuccess) {
-        if (graph) (void)hipGraphDestroy(graph);
-        drop();
-        if (rc != QTX_OK) return rc;
-        HIPCHK(e);
-      }
-      hipGraphExec_t exec = nullptr;
-      e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (e != hipSuccess) { drop(); HIPCHK(e); }
-      execs.push_back(exec);
-    }
-    GraphEntry ent;
-    ent.execs = std::move(execs);
-    it = mm->graphs.emplace(key, std::move(ent)).first;
-  }
-  // One sub-batch (or one joint graph): replay on the caller's stream itself (a graph
-  // captured on one stream can be launched on any).  Several: fork to the model's streams
-  // and join back.
-  const bool fork = gr.G > 1 && !joint;
-  hipStream_t ls[QTX_MAX_GROUPS];
-  for (int i = 0; i < gr.G; ++i) ls[i] = fork ? mm->gstream[i] : st;
-  if (fork) {
-    HIPCHK(hipEventRecord(mm->ev_in, st));
-    for (int i = 0; i < gr.G; ++i) HIPCHK(hipStreamWaitEvent(ls[i], mm->ev_in, 0));
-  }
-  hipEvent_t tg0 = nullptr, tg1 = nullptr;   // QTX_TIME_GRAPH: diagnostic timing to stderr
-  const bool time_graph = knobs().time_graph;
-  if (time_graph) {
-    HIPCHK(hipEventCreate(&tg0));
-    HIPCHK(hipEventCreate(&tg1));
-    HIPCHK(hipEventRecord(tg0, ls[0]));
-  }
-  for (int t = 0; t < (max_len - 1) / per_graph; ++t)
-    for (int i = 0; i < (int)it->second.execs.size(); ++i) HIPCHK(hipGraphLaunch(it->second.execs[i], ls[i]));
-  if (time_graph) {
-    float ms = 0.0f;
-    HIPCHK(hipEventRecord(tg1, ls[0]));
-    HIPCHK(hipEventSynchronize(tg1));
-    HIPCHK(hipEventElapsedTime(&ms, tg0, tg1));
-    fprintf(stderr, "qtx: decode graphs %.3f ms (%d steps, group 0)\n", ms, max_len - 1);
-    (void)hipEventDestroy(tg0);
-    (void)hipEventDestroy(tg1);
-  }
-  if (fork)
-    for (int i = 0; i < gr.G; ++i) {
-      HIPCHK(hipEventRecord(mm->ev_out[i], ls[i]));
-      HIPCHK(hipStreamWaitEvent(st, mm->ev_out[i], 0));
-    }
-  // completion marker of this entry's replays (after the join: covers every sub-batch)
-  if (!it->second.done) HIPCHK(hipEventCreateWithFlags(&it->second.done, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(it->second.done, st));
-  return QTX_OK;
+  rq.key.host_pos = per_graph == max_len - 1;
+  rq.key.joint = gr.G > 1 && knobs().group_graph;
+  rq.step = [&](int i, hipStream_t s, int t) {
+    return greedy_step_fused(m, gv[i], gr.rows(i, B), S, max_len, ids + (long)gr.b0(i) * max_len,
+                             src_mask + (long)gr.b0(i) * S, s, t);
+  };
+  rq.plan = {{per_graph, (max_len - 1) / per_graph, 0}};
+  rq.timed = knobs().time_graph;
+  return run_steps(m, rq, st);
 }
 
 }  // namespace
@@ -2061,104 +1926,20 @@ int dfault_steps(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, int
     HIPCHK(launch_embed(g.ids + (long)gr.b0(i) * max_len + t0, max_len, gr.rows(i, B), 1, nullptr,
                         t0, m->tgt_lut, c.tgt_vocab, m->pe, c.max_len, gv[i].dec.x, D, st));
   }
-  auto step_fn = [&](int i, hipStream_t s, int t) {
+  StepRequest rq;
+  rq.key.rows = B; rq.key.S = S; rq.key.max_len = max_len;
+  rq.key.groups = gr.G;
+  rq.key.anchor = g.gsteps;
+  rq.key.form = g.top_ids ? StepForm::DfaultScored : StepForm::Dfault;   // this entry's own graphs
+  rq.step = [&](int i, hipStream_t s, int t) {
     return greedy_step_fused(m, gv[i], gr.rows(i, B), S, max_len, g.ids + (long)gr.b0(i) * max_len,
                              g.mask + (long)gr.b0(i) * S, s, t);
   };
-  qtx_model* mm = const_cast<qtx_model*>(m);
-  std::lock_guard<std::mutex> lock(mm->mu);
-  DeviceGuard dg(mm->device);
-  if (!mm->ev_in) HIPCHK(hipEventCreateWithFlags(&mm->ev_in, hipEventDisableTiming));
-  for (int i = 0; i < gr.G; ++i)
-    if (!mm->gstream[i]) {
-      HIPCHK(hipStreamCreateWithFlags(&mm->gstream[i], hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&mm->ev_out[i], hipEventDisableTiming));
-    }
-  const bool fork = gr.G > 1;
-  hipStream_t ls[QTX_MAX_GROUPS];
-  for (int i = 0; i < gr.G; ++i) ls[i] = fork ? mm->gstream[i] : st;
-  auto fork_in = [&]() -> int {
-    if (!fork) return QTX_OK;
-    HIPCHK(hipEventRecord(mm->ev_in, st));
-    for (int i = 0; i < gr.G; ++i) HIPCHK(hipStreamWaitEvent(ls[i], mm->ev_in, 0));
-    return QTX_OK;
-  };
-  auto join_out = [&]() -> int {
-    if (!fork) return QTX_OK;
-    for (int i = 0; i < gr.G; ++i) {
-      HIPCHK(hipEventRecord(mm->ev_out[i], ls[i]));
-      HIPCHK(hipStreamWaitEvent(st, mm->ev_out[i], 0));
-    }
-    return QTX_OK;
-  };
-  if (knobs().no_graph) {
-    RC(fork_in());
-    for (int t = t0; t < t1; ++t)
-      for (int i = 0; i < gr.G; ++i) RC(step_fn(i, ls[i], t));
-    return join_out();
-  }
   const int big = knobs().graph_steps > 0 ? knobs().graph_steps : 8;
-  const Knobs& kn = knobs();
-  const std::string variant = std::to_string(knobs_generation()) + ":" + std::to_string(kn.split_ln) +
-                              std::to_string(kn.ffn_qkernel) + std::to_string(kn.device_step) +
-                              (g.top_ids ? "ds" : "d");   // this entry's own graphs
-  auto key_of = [&](int per) { return GraphKey{B, S, max_len, gr.G * 1000 + per, g.gsteps, variant}; };
-  // one graph of `per` steps per sub-batch, captured on first use
-  auto ensure = [&](int per) -> int {
-    if (mm->graphs.find(key_of(per)) != mm->graphs.end()) return QTX_OK;
-    if (mm->graphs.size() >= 16) mm->clear_graphs();
-    std::vector<hipGraphExec_t> execs;
-    auto drop = [&] {
-      for (hipGraphExec_t e : execs) (void)hipGraphExecDestroy(e);
-    };
-    for (int i = 0; i < gr.G; ++i) {
-      hipGraph_t graph = nullptr;
-      hipError_t e = hipStreamBeginCapture(mm->gstream[i], hipStreamCaptureModeThreadLocal);
-      if (e != hipSuccess) { drop(); HIPCHK(e); }
-      int rc = QTX_OK;
-      for (int t = 0; t < per && rc == QTX_OK; ++t) rc = step_fn(i, mm->gstream[i], -1);
-      e = hipStreamEndCapture(mm->gstream[i], &graph);
-      if (rc != QTX_OK || e != hipSuccess) {
-        if (graph) (void)hipGraphDestroy(graph);
-        drop();
-        if (rc != QTX_OK) return rc;
-        HIPCHK(e);
-      }
-      hipGraphExec_t exec = nullptr;
-      e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (e != hipSuccess) { drop(); HIPCHK(e); }
-      execs.push_back(exec);
-    }
-    GraphEntry ent;
-    ent.execs = std::move(execs);
-    mm->graphs.emplace(key_of(per), std::move(ent));
-    return QTX_OK;
-  };
   const int nbig = big > 1 ? (t1 - t0) / big : 0, none = (t1 - t0) - nbig * big;
-  for (int pass = 0; pass < 2; ++pass) {   // (a capture may clear the cache: look again)
-    if (nbig) RC(ensure(big));
-    if (none) RC(ensure(1));
-  }
-  std::vector<std::pair<int, int>> plan;   // (steps per graph, replays)
-  if (nbig) plan.push_back({big, nbig});
-  if (none) plan.push_back({1, none});
-  for (const auto& pr : plan)
-    if (mm->graphs.find(key_of(pr.first)) == mm->graphs.end())
-      return fail(QTX_E_HIP, "decode graph missing");
-  RC(fork_in());
-  for (const auto& pr : plan) {
-    auto it = mm->graphs.find(key_of(pr.first));
-    for (int r = 0; r < pr.second; ++r)
-      for (int i = 0; i < gr.G; ++i) HIPCHK(hipGraphLaunch(it->second.execs[i], ls[i]));
-  }
-  RC(join_out());
-  for (const auto& pr : plan) {   // completion markers (after the join: every sub-batch)
-    auto it = mm->graphs.find(key_of(pr.first));
-    if (!it->second.done) HIPCHK(hipEventCreateWithFlags(&it->second.done, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(it->second.done, st));
-  }
-  return QTX_OK;
+  if (nbig) rq.plan.push_back({big, nbig, t0});
+  if (none) rq.plan.push_back({1, none, t0 + nbig * big});
+  return run_steps(m, rq, st);
 }
 
 // The faulty full-prefix decoder pass of step `step` over the whole batch (the fault's row
@@ -2204,9 +1985,7 @@ void dfault_store(const qtx_model* m, const void* ws, const qtx_model::DfaultHdr
 
 int dfault_args(const qtx_model* m, int B, int S, int max_len, const qtx_fault* f, int fault_step) {
   const qtx_config& c = m->cfg;
-  if (B <= 0 || S <= 0 || S > 512 || max_len < 1 || max_len > 512 || max_len > c.max_len ||
-      S > c.max_len)
-    return fail(QTX_E_INVALID, "bad shape B=%d S=%d max_len=%d", B, S, max_len);
+  RC(check_decode_shape(c, B, S, max_len));
   if ((long)B * c.tgt_vocab >= (1L << 30) || (long)B * max_len * c.d_model >= (1L << 30))
     return fail(QTX_E_INVALID, "B * tgt_vocab and B * max_len * d_model must be below 2^30");
   if (!f || f->kind == QTX_FAULT_NONE || f->module != 1)
@@ -2397,14 +2176,7 @@ int beam_prologue(const qtx_model* m, BeamWS& w, const int64_t* src, int B, int 
   const qtx_config& c = m->cfg;
   const long D = c.d_model, S4 = (S + 3) & ~3;
   GreedyWS& g = w.g;
-  HIPCHK(launch_embed(src, S, B, S, nullptr, 0, m->src_lut, c.src_vocab, m->pe, c.max_len,
-                      g.enc.x, (long)S * D, st));
-  RC(encoder_run(m, g.enc.x, w.mask_b, B, S, g.memory, g.enc, st, nullptr));
-  RC(cross_kv(m, g.memory, B * S, w.cross_b, st));
-  if (fused) {
-    const long v_ls = c.n_layers > 1 ? (long)(w.cross_b.v8[1] - w.cross_b.v8[0]) : 0;
-    HIPCHK(launch_vgroup4(w.cross_b.v8[0], v_ls, c.n_layers, B, S, w.cvg_b, (long)B * S4 * D, st));
-  }
+  RC(encode_src(m, g, src, w.mask_b, B, S, w.cross_b, fused ? w.cvg_b : nullptr, nullptr, st));
   for (int l = 0; l < c.n_layers; ++l) {
     HIPCHK(launch_beam_rep(w.cross_b.k8[l], g.cross.k8[l], B, K, S * D, st));
     if (fused)
@@ -2429,53 +2201,23 @@ int beam_prologue(const qtx_model* m, BeamWS& w, const int64_t* src, int B, int 
 int beam_steps(const qtx_model* m, BeamWS& w, int R, int S, int max_len, int n, int big,
                bool fused, hipStream_t st) {
   GreedyWS& g = w.g;
-  if (!fused || knobs().no_graph) {
-    for (int t = 0; t < n; ++t)
-      RC(fused ? greedy_step_fused(m, g, R, S, max_len, nullptr, g.mask, st, -1)
-               : greedy_step_unfused(m, g, R, S, max_len, nullptr, g.mask, st));
+  if (!fused) {
+    for (int t = 0; t < n; ++t) RC(greedy_step_unfused(m, g, R, S, max_len, nullptr, g.mask, st));
     return QTX_OK;
   }
-  qtx_model* mm = const_cast<qtx_model*>(m);
-  std::lock_guard<std::mutex> lock(mm->mu);
-  DeviceGuard dg(mm->device);
-  if (!mm->gstream[0]) {
-    HIPCHK(hipStreamCreateWithFlags(&mm->gstream[0], hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&mm->ev_out[0], hipEventDisableTiming));
-  }
-  const Knobs& kn = knobs();
-  const BeamTail& bt = w.tail;
   // the beam step's own graphs: the select's eos / pad are baked into the captured launch
-  const std::string variant = std::to_string(knobs_generation()) + ":" + std::to_string(kn.split_ln) +
-                              std::to_string(kn.ffn_qkernel) + std::to_string(kn.device_step) +
-                              "b" + std::to_string(bt.eos) + "," + std::to_string(bt.pad);
+  const BeamTail& bt = w.tail;
+  StepRequest rq;
+  rq.key.rows = R; rq.key.S = S; rq.key.max_len = max_len;
+  rq.key.anchor = g.step;
+  rq.key.form = StepForm::Beam;
+  rq.key.beam_k = bt.K; rq.key.eos = bt.eos; rq.key.pad = bt.pad;
+  rq.step = [&](int, hipStream_t s, int t) {
+    return greedy_step_fused(m, g, R, S, max_len, nullptr, g.mask, s, t);
+  };
   const int per = n == big ? big : 1;
-  const GraphKey key{R, S, max_len, bt.K * 100000 + per, g.step, variant};
-  auto it = mm->graphs.find(key);
-  if (it == mm->graphs.end()) {
-    if (mm->graphs.size() >= 16) mm->clear_graphs();
-    hipGraph_t graph = nullptr;
-    HIPCHK(hipStreamBeginCapture(mm->gstream[0], hipStreamCaptureModeThreadLocal));
-    int rc = QTX_OK;
-    for (int t = 0; t < per && rc == QTX_OK; ++t)
-      rc = greedy_step_fused(m, g, R, S, max_len, nullptr, g.mask, mm->gstream[0], -1);
-    const hipError_t e = hipStreamEndCapture(mm->gstream[0], &graph);
-    if (rc != QTX_OK || e != hipSuccess) {
-      if (graph) (void)hipGraphDestroy(graph);
-      if (rc != QTX_OK) return rc;
-      HIPCHK(e);
-    }
-    hipGraphExec_t exec = nullptr;
-    const hipError_t e2 = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    HIPCHK(e2);
-    GraphEntry ent;
-    ent.execs.push_back(exec);
-    it = mm->graphs.emplace(key, std::move(ent)).first;
-  }
-  for (int r = 0; r < n / per; ++r) HIPCHK(hipGraphLaunch(it->second.execs[0], st));
-  if (!it->second.done) HIPCHK(hipEventCreateWithFlags(&it->second.done, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(it->second.done, st));
-  return QTX_OK;
+  rq.plan = {{per, n / per, -1}};
+  return run_steps(m, rq, st);
 }
 
 }  // namespace
@@ -2496,9 +2238,7 @@ int32_t qtx_beam_decode(const qtx_model* m, const int64_t* src, const uint8_t* s
   if (!m || !src || !src_mask || !hyp_ids || !hyp_score || !hyp_len || !ws)
     return fail(QTX_E_INVALID, "null argument");
   const qtx_config& c = m->cfg;
-  if (B <= 0 || S <= 0 || S > 512 || max_len < 1 || max_len > 512 || max_len > c.max_len ||
-      S > c.max_len)
-    return fail(QTX_E_INVALID, "bad shape B=%d S=%d max_len=%d", B, S, max_len);
+  RC(check_decode_shape(c, B, S, max_len));
   if (const int lim = beam_limits(B, beam, c.tgt_vocab, start, eos, pad); lim != QTX_OK)
     return fail(lim, "beam decode: 1 <= beam <= 8, beam <= tgt_vocab, start / eos / pad inside "
                      "the vocabulary, eos != pad, B * beam * tgt_vocab < 2^30 (beam=%d eos=%lld "
@@ -2700,7 +2440,7 @@ int32_t qtx_score_targets(const qtx_model* m, const int64_t* src, const uint8_t*
   if (!top_ids != !top_logp) return fail(QTX_E_INVALID, "top_ids and top_logp come as a pair");
   const qtx_config& c = m->cfg;
   const int K = tgt_per_src, T = L - 1;
-  if (B <= 0 || S <= 0 || S > 512 || S > c.max_len || L < 2 || T > 512 || T > c.max_len || K < 1)
+  if (bad_decode_shape(c, B, S, T) || K < 1)
     return fail(QTX_E_INVALID, "bad shape B=%d S=%d L=%d tgt_per_src=%d", B, S, L, K);
   if (c.tgt_vocab < 2) return fail(QTX_E_INVALID, "scoring needs tgt_vocab >= 2 (%d)", c.tgt_vocab);
   if (n_faults < 0 || (n_faults > 0 && !faults))
@@ -2996,6 +2736,15 @@ int32_t qtx_decode_attention(int32_t kv_new, const float* y, int64_t ldy, int8_t
   a.step = step_dev; a.S = S; a.mask = mask; a.kv_new = kv_new;
   a.ctx = ctx; a.pmax = pmax; a.B = B;
   HIPCHK(launch_dec_attn(a, B, (hipStream_t)stream));
+  return QTX_OK;
+}
+
+int32_t qtx_debug_graph_stats(const qtx_model* m, int32_t* entries, int64_t* captures) {
+  if (!m || !entries || !captures) return fail(QTX_E_INVALID, "null argument");
+  qtx_model* mm = const_cast<qtx_model*>(m);
+  std::lock_guard<std::mutex> lock(mm->mu);
+  *entries = (int32_t)mm->sg.entries();
+  *captures = mm->sg.captures();
   return QTX_OK;
 }
 

@@ -18,7 +18,8 @@ SOURCES = ["qtx_kernels.hip", "qtx_decode.hip", "qtx_gemm.hip", "qtx_wsgemm.hip"
 # measured-negative kernel variants and their switches: compiled only into the diagnostic
 # library (build(extra=...) -> libqtx_diag.so, with -DQTX_DIAG), never into libqtx.so
 DIAG_SOURCES = ["diag/qtx_wsgemm_diag.hip"]   # csrc/diag/: outside the product sources
-HEADERS = ["qtx_common.h", "qtx_kernels.h", "qtx_ws.h", "qtx_knobs.h", "qtx_beam.h", "qtx_carve.h"]
+HEADERS = ["qtx_common.h", "qtx_kernels.h", "qtx_ws.h", "qtx_knobs.h", "qtx_beam.h", "qtx_carve.h",
+           "qtx_stepgraph.h"]
 
 # -ffp-contract=off: every float op is a separate IEEE op (the numerics contract,
 # DESIGN.md §3); HIP keeps correctly rounded fp32 '/' and sqrtf by default.

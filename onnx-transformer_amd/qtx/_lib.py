@@ -117,6 +117,7 @@ SIGNATURES = {
     "qtx_decode_top2_embed": (I32, [P, P, I32, P, I64, P, P, P, P, P]),
     "qtx_decode_generator": (I32, [P, P, I32, P, P, P]),
     "qtx_debug_nop": (I32, [P]),
+    "qtx_debug_graph_stats": (I32, [P, C.POINTER(I32), C.POINTER(I64)]),
     "qtx_debug_reload_knobs": (I32, []),
     "qtx_model_check": (I32, [P, P]),
 }
