@@ -3,6 +3,8 @@
 // GEMM variants that were measured and not kept, kept reproducible for A/B
 // runs: k_gemm_wsz / k_gemm_wsa / k_gemm_wsa2 (round 4), k_gemm_wss and k_gemm_wsx (round 3).
 // launch_gemm_ws_diag() is consulted by launch_gemm_ws / launch_gemm_wsx in QTX_DIAG builds.
+// The kernels share their parts with the product kernels (qtx_ws.h; their asm MFMA statements
+// for W in AGPRs and for the 32x32x32 MFMA are there too, under QTX_DIAG).
 #include <cstdlib>
 #include <type_traits>
 
@@ -46,80 +48,31 @@ __global__ __launch_bounds__(512) void k_gemm_wsz(RowGemmArgs g) {
   const int f = lane & 15, gq = lane >> 4;
   const int nsl = g.N >> 9;
   const int wpt = gridDim.x / nsl;
-  int t = blockIdx.x % nsl, r0 = blockIdx.x / nsl;
-  if (XG) {          // the slices of a row group on one XCD (speed only), as k_gemm_wsq
-    const int b = blockIdx.x, A = gridDim.x / (8 * nsl), aligned = 8 * nsl * A;
-    if (b < aligned) {
-      const int j = b >> 3;
-      t = j % nsl;
-      r0 = 8 * (j / nsl) + (b & 7);
-    } else {
-      t = (b - aligned) % nsl;
-      r0 = 8 * A + (b - aligned) / nsl;
-    }
-  }
+  int t, r0;
+  ws_assign<XG>(nsl, t, r0);      // the slices of a row group on one XCD (speed only)
   const int nb = (g.M + WP_R - 1) / WP_R;
   if (r0 >= nb) return;
-  const int nblk = (nb - r0 + wpt - 1) / wpt;
+  const WsWalk wk(r0, wpt, nb);
+  const int nblk = wk.nblk;
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto dma4 = [](const float* gsrc, const float* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto rbk = [&](int k) { return r0 + min(k, nblk - 1) * wpt; };
-  auto issue = [&](int k) {
-    uint8_t* st = lds + (k & 1) * WP_STAGE;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const long row = min(rbk(k) * WP_R + 16 * i + f, g.M - 1);
-      dma16(g.A + kp_off(row, 64 * wave + 16 * gq, WS_K), st + ((wave * 2 + i) << 10));
-    }
-    dma4(g.sa + min(rbk(k) * WP_R + (lane & 31), g.M - 1), sal + ((k % 3) * 8 + wave) * 64);
+  auto rbk = [&](int k) { return wk.rb(k); };
+  auto issue = [&](int k) {      // block k's A rows and its row scales
+    ws_issue<2, true>(g, lds + (k & 1) * WP_STAGE, sal + ((k % 3) * 8 + wave) * 64, rbk(k), wave, lane);
   };
   issue(0);
   v4i wr[SR][4];
-  {
-    const int8_t* wsrc = g.W + ((long)(t * 8 + wave) << 15);
-    const v4i* ws = reinterpret_cast<const v4i*>(wsrc) + lane;
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) wr[s][j] = ws[(s * 4 + j) * 64];
-#pragma unroll
-    for (int p = 0; p < (8 - SR) * 4; ++p)
-      dma16(wsrc + ((SR * 4 + p) << 10) + lane * 16, wl + ((wave * (8 - SR) * 4 + p) << 10));
-    if (wave < 4) {
-      const int c = 128 * wave + 2 * lane;
-      *reinterpret_cast<float2*>(swl + c) = *reinterpret_cast<const float2*>(g.sw + 512 * t + c);
-      *reinterpret_cast<float2*>(swl + 512 + c) = *reinterpret_cast<const float2*>(g.bias + 512 * t + c);
-    }
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(wr[s][j]));
-  }
+  ws_load_w(wr, wl, g, t, wave, lane);
+  ws_fill_sw(swl, g, t, wave, lane);
+  ws_hold_w(wr);
   const int cs = 64 * wave + 16 * gq;
   const __amdgpu_buffer_rsrc_t orsrc = ws_rsrc(g.out8 + (long)t * g.o8_ts, (long)g.M * g.ldo8);
   const __amdgpu_buffer_rsrc_t srsrc = ws_rsrc(g.os + (long)t * g.os_ts, 4L * g.M);
-  auto redb = [&](int k) { return red0 + (k & 1) * 8 * WP_R; };
+  auto redb = [&](int k) { return ws_redb(red0, k); };
 
   // block k's scale per row (lane: row lane & 31) from its complete partial maxima, stored;
   // broadcast per row fragment: divisor bq, reciprocal iq
   auto scales = [&](int k, float (&bq)[2], float (&iq)[2]) {
-    const float* red = redb(k);
-    float m = red[lane & 31];
-#pragma unroll
-    for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w * WP_R + (lane & 31)]);
+    const float m = ws_slice_max(redb(k), lane & 31);
     const float sc = fmaxf(m, 1e-5f) / 127.0f;
     const float inv = 1.0f / sc;
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sc), srsrc, 4 * (rbk(k) * WP_R + (lane & 31)), 0, 0);
@@ -343,26 +296,6 @@ __global__ __launch_bounds__(512) void k_gemm_wsz(RowGemmArgs g) {
 //                 folded) after every odd one; block k-1's partial row maxima -> red.
 // Numerics: exactly k_gemm_wsq's (the same canonical operations per output).
 // =====================================================================================
-template <bool Z, typename T>
-__device__ __forceinline__ void mfma_pin_a(v4i& acc, const v4i& w, const v4i& a, float before, T& after) {
-  if constexpr (Z)
-    asm volatile("v_mfma_i32_16x16x64_i8 %0, %2, %3, 0" : "=&v"(acc), "+v"(after) : "a"(w), "v"(a), "v"(before));
-  else
-    asm volatile("v_mfma_i32_16x16x64_i8 %0, %2, %3, %0" : "+v"(acc), "+v"(after) : "a"(w), "v"(a), "v"(before));
-}
-template <bool Z>
-__device__ __forceinline__ void mfma_asm_a(v4i& acc, const v4i& w, const v4i& a) {
-  if constexpr (Z)
-    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, 0" : "=&v"(acc) : "a"(w), "v"(a));
-  else
-    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(a));
-}
-__device__ __forceinline__ void mfma_settle8(v4i (&acc)[8]) {
-  asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 4"
-               : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]),
-                 "+v"(acc[4]), "+v"(acc[5]), "+v"(acc[6]), "+v"(acc[7]));
-}
-
 template <int XG = 1>
 __global__ __launch_bounds__(256, 1) void k_gemm_wsa(RowGemmArgs g) {
   constexpr int NS = 3;                                      // A stages (prefetch distance 2)
@@ -376,37 +309,14 @@ __global__ __launch_bounds__(256, 1) void k_gemm_wsa(RowGemmArgs g) {
   const int f = lane & 15, gq = lane >> 4;
   const int nsl = g.N >> 9;
   const int wpt = gridDim.x / nsl;
-  int t = blockIdx.x % nsl, r0 = blockIdx.x / nsl;
-  if (XG) {          // the slices of a row group on one XCD (speed only), as k_gemm_wsq
-    const int b = blockIdx.x, A = gridDim.x / (8 * nsl), aligned = 8 * nsl * A;
-    if (b < aligned) {
-      const int j = b >> 3;
-      t = j % nsl;
-      r0 = 8 * (j / nsl) + (b & 7);
-    } else {
-      t = (b - aligned) % nsl;
-      r0 = 8 * A + (b - aligned) / nsl;
-    }
-  }
+  int t, r0;
+  ws_assign<XG>(nsl, t, r0);      // the slices of a row group on one XCD (speed only)
   const int nb = (g.M + R - 1) / R;
   if (r0 >= nb) return;
-  const int nblk = (nb - r0 + wpt - 1) / wpt;
+  const WsWalk wk(r0, wpt, nb);
+  const int nblk = wk.nblk;
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto dma4 = [](const float* gsrc, const float* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto rbk = [&](int k) { return r0 + min(k, nblk - 1) * wpt; };
+  auto rbk = [&](int k) { return wk.rb(k); };
   // block k's A (wave w: K steps 2w, 2w+1) and row scales: 3 VM operations per wave
   constexpr int WSA_DMA_OPS = 3;
   auto issue = [&](int k) {
@@ -415,9 +325,9 @@ __global__ __launch_bounds__(256, 1) void k_gemm_wsa(RowGemmArgs g) {
     for (int ss = 0; ss < 2; ++ss) {
       const int s = 2 * wave + ss;
       const long row = min(rbk(k) * R + f, g.M - 1);
-      dma16(g.A + kp_off(row, 64 * s + 16 * gq, WS_K), st + (s << 10));
+      lds_dma16(g.A + kp_off(row, 64 * s + 16 * gq, WS_K), st + (s << 10));
     }
-    dma4(g.sa + min(rbk(k) * R + f, g.M - 1), sal + ((k % 3) * 4 + wave) * 64);
+    lds_dma4(g.sa + min(rbk(k) * R + f, g.M - 1), sal + ((k % 3) * 4 + wave) * 64);
   };
   // W: fragment (s, jn) of this wave = WS-layout fragment (s, jn & 3) of 64-column group
   // 2w + (jn >> 2) (k_pack_w_ws); used only as the MFMAs' "a" operand: it lives in AGPRs
@@ -646,37 +556,14 @@ __global__ __launch_bounds__(256, 1) void k_gemm_wsa2(RowGemmArgs g) {
   const int f = lane & 15, gq = lane >> 4;
   const int nsl = g.N >> 9;
   const int wpt = gridDim.x / nsl;
-  int t = blockIdx.x % nsl, r0 = blockIdx.x / nsl;
-  if (XG) {
-    const int b = blockIdx.x, A = gridDim.x / (8 * nsl), aligned = 8 * nsl * A;
-    if (b < aligned) {
-      const int j = b >> 3;
-      t = j % nsl;
-      r0 = 8 * (j / nsl) + (b & 7);
-    } else {
-      t = (b - aligned) % nsl;
-      r0 = 8 * A + (b - aligned) / nsl;
-    }
-  }
+  int t, r0;
+  ws_assign<XG>(nsl, t, r0);      // the slices of a row group on one XCD (speed only)
   const int nb = (g.M + R - 1) / R;
   if (r0 >= nb) return;
-  const int nblk = (nb - r0 + wpt - 1) / wpt;
+  const WsWalk wk(r0, wpt, nb);
+  const int nblk = wk.nblk;
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto dma4 = [](const float* gsrc, const float* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto rbk = [&](int k) { return r0 + min(k, nblk - 1) * wpt; };
+  auto rbk = [&](int k) { return wk.rb(k); };
   auto slot = [&](int k, int p) { return sal + (((k % 3) * (1 + NPM) + p) * 4 + wave) * 64; };
   constexpr int DMA_OPS = 3 + NPM;
   auto issue = [&](int k) {
@@ -685,11 +572,11 @@ __global__ __launch_bounds__(256, 1) void k_gemm_wsa2(RowGemmArgs g) {
 #pragma unroll
     for (int ss = 0; ss < 2; ++ss) {
       const int s = 2 * wave + ss;
-      dma16(g.A + kp_off(row, 64 * s + 16 * gq, WS_K), st + (s << 10));
+      lds_dma16(g.A + kp_off(row, 64 * s + 16 * gq, WS_K), st + (s << 10));
     }
-    dma4(g.sa + row, slot(k, 0));
+    lds_dma4(g.sa + row, slot(k, 0));
 #pragma unroll
-    for (int p = 0; p < NPM; ++p) dma4(g.pmax_in + (long)min(p, g.pmax_n - 1) * g.M + row, slot(k, 1 + p));
+    for (int p = 0; p < NPM; ++p) lds_dma4(g.pmax_in + (long)min(p, g.pmax_n - 1) * g.M + row, slot(k, 1 + p));
   };
   v4i wa[8][8];
 #pragma unroll
@@ -888,75 +775,30 @@ __global__ __launch_bounds__(512) void k_gemm_wss(RowGemmArgs g) {
   const bool grpB = __builtin_amdgcn_readfirstlane(wave) >= 4;
   const int nsl = g.N >> 9;
   const int wpt = gridDim.x / nsl;
-  const int t = blockIdx.x % nsl, r0 = blockIdx.x / nsl;
+  int t, r0;
+  ws_assign<0>(nsl, t, r0);
   const int nb = (g.M + WP_R - 1) / WP_R;
   if (r0 >= nb) return;
-  const int nblk = (nb - r0 + wpt - 1) / wpt;
+  const WsWalk wk(r0, wpt, nb);
+  const int nblk = wk.nblk;
   if (tid == 0) ydone = 0u;
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto rbk = [&](int k) { return r0 + min(k, nblk - 1) * wpt; };
-  auto dma4 = [](const float* gsrc, const float* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto issue = [&](int k) {      // block k's A rows and its row scales (as k_gemm_wsq)
-    uint8_t* st = lds + (k & 1) * WP_STAGE;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const long row = min(rbk(k) * WP_R + 16 * i + f, g.M - 1);
-      dma16(g.A + kp_off(row, 64 * wave + 16 * gq, WS_K), st + ((wave * 2 + i) << 10));
-    }
-    dma4(g.sa + min(rbk(k) * WP_R + (lane & 31), g.M - 1), sal + ((k & 1) * 8 + wave) * 64);
+  auto rbk = [&](int k) { return wk.rb(k); };
+  auto issue = [&](int k) {      // block k's A rows and its row scales
+    ws_issue<2, true>(g, lds + (k & 1) * WP_STAGE, sal + ((k & 1) * 8 + wave) * 64, rbk(k), wave, lane);
   };
   issue(0);
   v4i wr[SR][4];
-  {
-    const int8_t* wsrc = g.W + ((long)(t * 8 + wave) << 15);
-    const v4i* ws = reinterpret_cast<const v4i*>(wsrc) + lane;
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) wr[s][j] = ws[(s * 4 + j) * 64];
-#pragma unroll
-    for (int p = 0; p < (8 - SR) * 4; ++p)
-      dma16(wsrc + ((SR * 4 + p) << 10) + lane * 16, wl + ((wave * (8 - SR) * 4 + p) << 10));
-    if (wave < 4) {
-      const int c = 128 * wave + 2 * lane;
-      *reinterpret_cast<float2*>(swl + c) = *reinterpret_cast<const float2*>(g.sw + 512 * t + c);
-      *reinterpret_cast<float2*>(swl + 512 + c) = *reinterpret_cast<const float2*>(g.bias + 512 * t + c);
-    }
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(wr[s][j]));
-  }
+  ws_load_w(wr, wl, g, t, wave, lane);
+  ws_fill_sw(swl, g, t, wave, lane);
+  ws_hold_w(wr);
   const int cs = 64 * wave + 16 * gq;
   const __amdgpu_buffer_rsrc_t orsrc = ws_rsrc(g.out8 + (long)t * g.o8_ts, (long)g.M * g.ldo8);
   const __amdgpu_buffer_rsrc_t srsrc = ws_rsrc(g.os + (long)t * g.os_ts, 4L * g.M);
-  auto redb = [&](int k) { return red0 + (k & 1) * 8 * WP_R; };
+  auto redb = [&](int k) { return ws_redb(red0, k); };
   auto sr_of = [&](int k, float (&sr)[2]) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) sr[i] = sal[((k & 1) * 8 + wave) * 64 + 16 * i + f];
-  };
-  auto top_wait = [&]() {
-    __builtin_amdgcn_s_waitcnt(WAIT_VM(0));      // the block's DMA and the stores after it (VM_CNT_ORDER)
-    __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-    __builtin_amdgcn_s_barrier();
-  };
-  auto dummy_stores = [&]() {
-    const __amdgpu_buffer_rsrc_t nul = ws_rsrc(g.out8, 0L);
-#pragma unroll
-    for (int d2 = 0; d2 < 3; ++d2) __builtin_amdgcn_raw_buffer_store_b32(0u, nul, 0, 0, 0);
   };
   // B's Y phases of blocks < j all done and visible (bounded: never hang)
   auto wait_y = [&](int j) {
@@ -970,37 +812,10 @@ __global__ __launch_bounds__(512) void k_gemm_wss(RowGemmArgs g) {
   };
   // Y: y of block k from acc (row scale sa) and the wave's partial row maxima -> red[k & 1]
   auto form_y = [&](v4i (&acc)[2][4], const float (&sr_in)[2], float (&y)[2][16], int k) {
-    float sr[2];     // B: read at the top of its iteration, before the DMA reuses the stage
-#pragma unroll
-    for (int i = 0; i < 2; ++i) sr[i] = sr_in[i];
-    float am[2] = {0.0f, 0.0f};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float4 s4 = *reinterpret_cast<const float4*>(swl + cs + 4 * j);
-      const float4 b4 = *reinterpret_cast<const float4*>(swl + 512 + cs + 4 * j);
-      const float swj[4] = {s4.x, s4.y, s4.z, s4.w}, bj[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          y[i][4 * j + e] = ((float)acc[i][j][e] * sr[i]) * swj[e] + bj[e];
-          am[i] = fmaxf(am[i], fabsf(y[i][4 * j + e]));
-        }
-    }
-    float* red = redb(k);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      float a = am[i];
-      a = fmaxf(a, __shfl_xor(a, 16));
-      a = fmaxf(a, __shfl_xor(a, 32));
-      red[wave * WP_R + 16 * i + f] = a;
-    }
+    ws_form_y<false>(acc, sr_in, swl, redb(k), y, wave, lane);
   };
   auto scales = [&](int k, float (&bq)[2], float (&iq)[2]) {
-    const float* red = redb(k);
-    float m = red[lane & 31];
-#pragma unroll
-    for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w * WP_R + (lane & 31)]);
+    const float m = ws_slice_max(redb(k), lane & 31);
     const float sc = fmaxf(m, 1e-5f) / 127.0f;
     const float inv = 1.0f / sc;
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sc), srsrc, 4 * (rbk(k) * WP_R + (lane & 31)), 0, 0);
@@ -1029,53 +844,17 @@ __global__ __launch_bounds__(512) void k_gemm_wss(RowGemmArgs g) {
       store_row(k, i, d);
     }
   };
+  auto cvt = [](float yv, float bq, float iq) { return rint_biased(div_cr(yv, bq, iq)); };
+  auto pack = [](float t0, float t1, float t2, float t3) { return pack4_biased(t0, t1, t2, t3); };
   // M(k) into acc; Q: with Q(kq) of y between the MFMAs (pinned), 3 stores; else plain
   auto mfma_block = [&](v4i (&acc)[2][4], int k, auto q_c, int kq, float (&y)[2][16]) {
-    constexpr bool Q = decltype(q_c)::value;
-    const uint8_t* cur = lds + (k & 1) * WP_STAGE;
-    float bq[2] = {0.0f, 0.0f}, iq[2] = {0.0f, 0.0f};
-    if constexpr (Q) scales(kq, bq, iq);
-    float hist[3] = {0.0f, 0.0f, 0.0f}, tq[4];   // results of the last outputs, newest first
-    uint32_t d[4];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      v4i a[2], b[4];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const v4i*>(cur + ((s * 2 + i) << 10) + lane * 16);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        b[j] = s < SR ? wr[s < SR ? s : 0][j]
-                      : *reinterpret_cast<const v4i*>(wl + (((wave * (8 - SR) + s - SR) * 4 + j) << 10) + lane * 16);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = s * 8 + i * 4 + j;
-          if (!Q || (n & 1) == 0) {
-            if (s == 0) mfma_asm<true>(acc[i][j], b[j], a[i]);
-            else mfma_asm<false>(acc[i][j], b[j], a[i]);
-          } else {
-            const int o = n >> 1, ii = o >> 4, jj = (o >> 2) & 3, e = o & 3;
-            float yv = y[ii][4 * jj + e];
-            if (s == 0) mfma_pin<true>(acc[i][j], b[j], a[i], hist[LAG - 1], yv);
-            else mfma_pin<false>(acc[i][j], b[j], a[i], hist[LAG - 1], yv);
-            tq[e] = rint_biased(div_cr(yv, bq[ii], iq[ii]));
-            hist[2] = hist[1]; hist[1] = hist[0]; hist[0] = tq[e];
-            if (e == 3) {
-              d[jj] = pack4_biased(tq[0], tq[1], tq[2], tq[3]);
-              if (jj == 3) store_row(kq, ii, d);
-            }
-          }
-        }
-    }
-    mfma_settle(acc);
+    ws_mfma_block<LAG>(acc, wr, lds + (k & 1) * WP_STAGE, wl, wave, lane, decltype(q_c)::value, kq, y, scales, cvt,
+                       pack, store_row);
   };
   const std::true_type T_{};
   const std::false_type F_{};
 
-  __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-  __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-  __builtin_amdgcn_s_barrier();
+  ws_top_wait();
   // one loop per group (the same iterations and barriers): a loop shared by both would carry
   // the union of their loop-carried values (A: y, B: acc) and spill — and a spill reload's
   // wait is vmcnt(0), which also waits for the next block's DMA and every store
@@ -1083,14 +862,14 @@ __global__ __launch_bounds__(512) void k_gemm_wss(RowGemmArgs g) {
     v4i acc[2][4];
     float y[2][16];
     for (int k = 0; k <= nblk; ++k) {
-      if (k > 0) top_wait();
+      if (k > 0) ws_top_wait();
       if (k + 1 < nblk) issue(k + 1);
       if (k < nblk) mfma_block(acc, k, F_, 0, y);
       if (k >= 1) {
         wait_y(k);                          // B's partial maxima of block k-1
         quant_all(k - 1, y);
       } else {
-        dummy_stores();
+        ws_dummy_stores(g);
       }
       if (k < nblk) {
         float sr[2];
@@ -1102,7 +881,7 @@ __global__ __launch_bounds__(512) void k_gemm_wss(RowGemmArgs g) {
     v4i acc[2][4];
     float y[2][16];
     for (int k = 0; k <= nblk; ++k) {
-      if (k > 0) top_wait();
+      if (k > 0) ws_top_wait();
       float sr[2];
       if (k >= 1) {                         // block k-1's scales, before DMA(k+1) reuses the stage
         sr_of(k - 1, sr);
@@ -1118,7 +897,7 @@ __global__ __launch_bounds__(512) void k_gemm_wss(RowGemmArgs g) {
         if (k >= 1) mfma_block(acc, k, T_, k - 1, y);
         else {
           mfma_block(acc, k, F_, 0, y);
-          dummy_stores();
+          ws_dummy_stores(g);
         }
       } else {
         quant_all(k - 1, y);
@@ -1163,56 +942,20 @@ __global__ __launch_bounds__(512) void k_gemm_wsx(RowGemmArgs g) {
   // co-residency assumption, no deadlock.  The ticket counter follows the granules.
   const int nb = (g.M + WP_R - 1) / WP_R;
   unsigned long long* const gran = reinterpret_cast<unsigned long long*>(g.pmax_out);
-  __shared__ int ticket;
-  if (tid == 0)
-    ticket = (int)atomicAdd(reinterpret_cast<unsigned*>(gran + 4L * 32 * nb), 1u);
-  __syncthreads();
-  // slices of a row group at tickets 8 apart: workgroups start about in blockIdx order and
-  // are dealt round-robin to the 8 XCDs, so the 4 partners mostly share an XCD (speed only);
-  // a group is complete once its highest ticket has started (any 25 started tickets hold one)
-  const int q = ticket, wpt = gridDim.x >> 2;
-  const int t = (q >> 3) & 3, r0 = (q & 7) + 8 * (q >> 5);
+  int t, r0;
+  ws_assign_ticket(gran, nb, t, r0);
+  const int wpt = gridDim.x >> 2;
   if (r0 >= nb) return;                         // the whole row group (all 4 slices) skips
-  const int nblk = (nb - r0 + wpt - 1) / wpt;
+  const WsWalk wk(r0, wpt, nb);
+  const int nblk = wk.nblk;
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto rbk = [&](int k) { return r0 + min(k, nblk - 1) * wpt; };
-  auto issue = [&](int k) {
-    uint8_t* st = lds + (k & 1) * WP_STAGE;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const long row = min(rbk(k) * WP_R + 16 * i + f, g.M - 1);
-      dma16(g.A + kp_off(row, 64 * wave + 16 * gq, WS_K), st + ((wave * 2 + i) << 10));
-    }
-  };
+  auto rbk = [&](int k) { return wk.rb(k); };
+  auto issue = [&](int k) { ws_issue<2, false>(g, lds + (k & 1) * WP_STAGE, nullptr, rbk(k), wave, lane); };
   issue(0);
   v4i wr[SR][4];
-  {
-    const int8_t* wsrc = g.W + ((long)(t * 8 + wave) << 15);
-#pragma unroll
-    for (int p = 0; p < (8 - SR) * 4; ++p)
-      dma16(wsrc + ((SR * 4 + p) << 10) + lane * 16, wl + ((wave * (8 - SR) * 4 + p) << 10));
-    const v4i* ws = reinterpret_cast<const v4i*>(wsrc) + lane;
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) wr[s][j] = ws[(s * 4 + j) * 64];
-    if (wave < 4) {
-      const int c = 128 * wave + 2 * lane;
-      *reinterpret_cast<float2*>(swl + c) = *reinterpret_cast<const float2*>(g.sw + 512 * t + c);
-      *reinterpret_cast<float2*>(swl + 512 + c) = *reinterpret_cast<const float2*>(g.bias + 512 * t + c);
-    }
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(wr[s][j]));
-  }
+  ws_load_w<true>(wr, wl, g, t, wave, lane);
+  ws_fill_sw(swl, g, t, wave, lane);
+  ws_hold_w(wr);
   const int cs = 64 * wave + 16 * gq;
   const int c0 = 512 * t + cs;
   const __amdgpu_buffer_rsrc_t orsrc = ws_rsrc(g.out8, (long)(g.M + (g.M & 1)) * g.ldo8);
@@ -1223,11 +966,9 @@ __global__ __launch_bounds__(512) void k_gemm_wsx(RowGemmArgs g) {
     for (int s = s0; s < s1; ++s) {
       v4i a[2], b[4];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const v4i*>(cur + ((s * 2 + i) << 10) + lane * 16);
+      for (int i = 0; i < 2; ++i) a[i] = ws_piece(cur, s * 2 + i, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        b[j] = s < SR ? wr[s < SR ? s : 0][j]
-                      : *reinterpret_cast<const v4i*>(wl + (((wave * (8 - SR) + s - SR) * 4 + j) << 10) + lane * 16);
+      for (int j = 0; j < 4; ++j) b[j] = ws_bfrag(wr, wl, wave, lane, s, j);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1262,45 +1003,8 @@ __global__ __launch_bounds__(512) void k_gemm_wsx(RowGemmArgs g) {
       red[wave * WP_R + 16 * i + f] = a;
     }
   };
-  // the slice's row maximum of row (lane & 31) over its 8 waves (after a barrier)
-  auto slice_max = [&]() {
-    float m = red[lane & 31];
-#pragma unroll
-    for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w * WP_R + (lane & 31)]);
-    return m;
-  };
-  auto gidx = [&](int rb, int tt) { return ((long)rb * 4 + tt) * 32 + (lane & 31); };
-  auto publish = [&](int k, float m) {
-    if (wave == 0 && lane < 32)
-      __hip_atomic_store(gran + gidx(rbk(k), t), (1ull << 32) | __float_as_uint(m),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  // the row maximum over all 4 slices: this slice's, then the partners' granules (bounded)
-  const unsigned lim = (unsigned)g.spin_limit;
-  auto full_max = [&](int k, float mloc) {
-    const int rb = rbk(k);
-    float m = mloc;
-    for (unsigned spin = 0;; ++spin) {
-      bool ok = true;
-      float mx = mloc;
-#pragma unroll
-      for (int d = 1; d < 4; ++d) {
-        const unsigned long long v = __hip_atomic_load(gran + gidx(rb, (t + d) & 3), __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT);
-        ok &= (v >> 32) == 1ull;
-        mx = fmaxf(mx, __uint_as_float((unsigned)v));
-      }
-      if (__all(ok)) { m = mx; break; }
-      if (spin >= lim) {                            // bounded: never hang, never silent
-        if (lane == 0)
-          __hip_atomic_fetch_or(g.status, DEV_E_EXCHANGE_TIMEOUT, __ATOMIC_RELAXED,
-                                __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(2);
-    }
-    return m;
-  };
+  // the exchange of the slices' row maxima (this kernel predates the drop-slice test hook)
+  const WsExchange ex{gran, g.status, (unsigned)g.spin_limit, t, -1, lane & 31};
   auto quant_store = [&](int k, const float (&y)[2][16], float m) {
     const int m0 = rbk(k) * WP_R;
     const float sc = fmaxf(m, 1e-5f) / 127.0f;   // true division: branch-free (see k_gemm_wsp)
@@ -1336,9 +1040,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsx(RowGemmArgs g) {
   v4i accp[2][4];
   float yq[2][16];                  // y of the block waiting for its partners' maxima
   float mq = 0.0f;                  // ... and its own slice maximum
-  __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-  __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-  __builtin_amdgcn_s_barrier();
+  ws_top_wait();
   float sap = sa_of(0);
   issue(1);
   zero(accp);
@@ -1350,9 +1052,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsx(RowGemmArgs g) {
     // block k's DMA retired, and the previous iteration's stores (3 per wave, plus wave 0's
     // granule store) with it: VM_CNT_ORDER (qtx_common.h) — a store issued after the DMA
     // may retire before it, so vmcnt(3) could release the barrier with the DMA in flight
-    __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-    __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-    __builtin_amdgcn_s_barrier();
+    ws_top_wait();
     const bool more = k < nblk;     // block k exists (uniform)
     asm volatile("" ::"v"(sap));
     float sac = more ? sa_of(k) : 0.0f;
@@ -1365,18 +1065,16 @@ __global__ __launch_bounds__(512) void k_gemm_wsx(RowGemmArgs g) {
     form_y(accp, sap, y);           // block k-1
     __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
     __builtin_amdgcn_s_barrier();
-    const float mloc = slice_max(); // block k-1's slice maximum (red complete)
+    const float mloc = ws_slice_max(red, lane & 31);   // block k-1's slice maximum (red complete)
     float m2 = 0.0f;
-    if (k >= 2) m2 = full_max(k - 2, mq);
+    if (k >= 2) m2 = ex.full_max(rbk(k - 2), mq);
     if (more) mfma_steps(acc, cur, 4, 8);
     if (k >= 2) {
       quant_store(k - 2, yq, m2);
     } else {                        // the 3 stores the next top wait counts (range 0: dropped)
-      const __amdgpu_buffer_rsrc_t nul = ws_rsrc(g.out8, 0L);
-#pragma unroll
-      for (int d = 0; d < 3; ++d) __builtin_amdgcn_raw_buffer_store_b32(0u, nul, 0, 0, 0);
+      ws_dummy_stores(g);
     }
-    publish(k - 1, mloc);
+    if (wave == 0 && lane < 32) ex.publish(rbk(k - 1), mloc);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1389,28 +1087,8 @@ __global__ __launch_bounds__(512) void k_gemm_wsx(RowGemmArgs g) {
     sap = sac;
   }
   // ---- the last block: its partners' maxima, then its quantization
-  quant_store(nblk - 1, yq, full_max(nblk - 1, mq));
+  quant_store(nblk - 1, yq, ex.full_max(rbk(nblk - 1), mq));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// The same statements for v_mfma_i32_32x32x32_i8 (k_gemm_wsq32, this file): 16 accumulators per lane,
-// 16 passes, so the settle pad is 24 wait states.
-template <bool Z, typename T>
-__device__ __forceinline__ void mfma32_pin(v16i& acc, const v4i& w, const v4i& a, float before, T& after) {
-  if constexpr (Z)
-    asm volatile("v_mfma_i32_32x32x32_i8 %0, %2, %3, 0" : "=&v"(acc), "+v"(after) : "v"(w), "v"(a), "v"(before));
-  else
-    asm volatile("v_mfma_i32_32x32x32_i8 %0, %2, %3, %0" : "+v"(acc), "+v"(after) : "v"(w), "v"(a), "v"(before));
-}
-template <bool Z>
-__device__ __forceinline__ void mfma32_asm(v16i& acc, const v4i& w, const v4i& a) {
-  if constexpr (Z)
-    asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(a));
-  else
-    asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(a));
-}
-__device__ __forceinline__ void mfma32_settle(v16i (&acc)[2]) {
-  asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" : "+v"(acc[0]), "+v"(acc[1]));
 }
 
 // =====================================================================================
@@ -1447,37 +1125,14 @@ __global__ __launch_bounds__(512) void k_gemm_wsq32(RowGemmArgs g) {
   const int tok = lane & 31, hh = lane >> 5;
   const int nsl = g.N >> 9;
   const int wpt = gridDim.x / nsl;
-  int t = blockIdx.x % nsl, r0 = blockIdx.x / nsl;
-  if (XG) {
-    const int b = blockIdx.x, A = gridDim.x / (8 * nsl), aligned = 8 * nsl * A;
-    if (b < aligned) {
-      const int j = b >> 3;
-      t = j % nsl;
-      r0 = 8 * (j / nsl) + (b & 7);
-    } else {
-      t = (b - aligned) % nsl;
-      r0 = 8 * A + (b - aligned) / nsl;
-    }
-  }
+  int t, r0;
+  ws_assign<XG>(nsl, t, r0);      // the slices of a row group on one XCD (speed only)
   const int nb = (g.M + WP_R - 1) / WP_R;
   if (r0 >= nb) return;
-  const int nblk = (nb - r0 + wpt - 1) / wpt;
+  const WsWalk wk(r0, wpt, nb);
+  const int nblk = wk.nblk;
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto dma4 = [](const float* gsrc, const float* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto rbk = [&](int k) { return r0 + min(k, nblk - 1) * wpt; };
+  auto rbk = [&](int k) { return wk.rb(k); };
   // block k: wave w brings A pieces 2w, 2w + 1 and (as k_gemm_wsq) its copy of the 32 row scales
   auto issue = [&](int k) {
     uint8_t* st = lds + (k & 1) * WP_STAGE;
@@ -1485,40 +1140,18 @@ __global__ __launch_bounds__(512) void k_gemm_wsq32(RowGemmArgs g) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int s = 2 * wave + i;
-      dma16(g.A + kp_off(row, 32 * s + 16 * hh, WS_K), st + (s << 10));
+      lds_dma16(g.A + kp_off(row, 32 * s + 16 * hh, WS_K), st + (s << 10));
     }
-    dma4(g.sa + min(rbk(k) * WP_R + tok, g.M - 1), sal + ((k & 1) * 8 + wave) * 64);
+    lds_dma4(g.sa + min(rbk(k) * WP_R + tok, g.M - 1), sal + ((k & 1) * 8 + wave) * 64);
   };
   issue(0);
   v4i wr[SR][2];
-  {
-    const int8_t* wsrc = g.W + ((long)(t * 8 + wave) << 15);
-    const v4i* ws = reinterpret_cast<const v4i*>(wsrc) + lane;
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) wr[s][u] = ws[(s * 2 + u) * 64];
-#pragma unroll
-    for (int p = 0; p < (16 - SR) * 2; ++p)
-      dma16(wsrc + ((SR * 2 + p) << 10) + lane * 16, wl + ((wave * (16 - SR) * 2 + p) << 10));
-    if (wave < 4) {
-      const int c = 128 * wave + 2 * lane;
-      *reinterpret_cast<float2*>(swl + c) = *reinterpret_cast<const float2*>(g.sw + 512 * t + c);
-      *reinterpret_cast<float2*>(swl + 512 + c) = *reinterpret_cast<const float2*>(g.bias + 512 * t + c);
-    }
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) asm volatile("" ::"v"(wr[s][u]));
-  }
+  ws_load_w(wr, wl, g, t, wave, lane);
+  ws_fill_sw(swl, g, t, wave, lane);
+  ws_hold_w(wr);
   const __amdgpu_buffer_rsrc_t orsrc = ws_rsrc(g.out8 + (long)t * g.o8_ts, (long)g.M * g.ldo8);
   const __amdgpu_buffer_rsrc_t srsrc = ws_rsrc(g.os + (long)t * g.os_ts, 4L * g.M);
-  auto redb = [&](int k) { return red0 + (k & 1) * 8 * WP_R; };
-  auto top_wait = [&]() {
-    __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-    __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-    __builtin_amdgcn_s_barrier();
-  };
+  auto redb = [&](int k) { return ws_redb(red0, k); };
   // y of block k and the wave's partial row maxima into red[k & 1]; lane: token tok,
   // columns 64 wave + 32 u + 16 hh + r
   auto form_y = [&](v16i (&acc)[2], float (&y)[2][16], int k) {
@@ -1543,10 +1176,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsq32(RowGemmArgs g) {
   };
   // the scale of block k's rows: lane's token only (no broadcast needed)
   auto scales = [&](int k, float& bq, float& iq) {
-    const float* red = redb(k);
-    float m = red[tok];
-#pragma unroll
-    for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w * WP_R + tok]);
+    const float m = ws_slice_max(redb(k), tok);
     bq = scale127(fmaxf(m, 1e-5f));
     iq = rcp_cr(bq);
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(bq), srsrc, 4 * (rbk(k) * WP_R + tok), 0, 0);
@@ -1592,27 +1222,23 @@ __global__ __launch_bounds__(512) void k_gemm_wsq32(RowGemmArgs g) {
     }
     mfma32_settle(acc);
     if (!q) {           // the 3 stores per iteration of the q path (dropped)
-      const __amdgpu_buffer_rsrc_t nul = ws_rsrc(g.out8, 0L);
-#pragma unroll
-      for (int d2 = 0; d2 < 3; ++d2) __builtin_amdgcn_raw_buffer_store_b32(0u, nul, 0, 0, 0);
+      ws_dummy_stores(g);
     }
   };
 
   v16i acc[2];
   float y[2][16];
-  __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-  __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-  __builtin_amdgcn_s_barrier();
+  ws_top_wait();
   issue(1);
   mfma_block(acc, lds, false, 0, y);
   form_y(acc, y, 0);
   for (int k = 1; k < nblk; ++k) {
-    top_wait();
+    ws_top_wait();
     issue(k + 1);
     mfma_block(acc, lds + (k & 1) * WP_STAGE, true, k - 1, y);
     form_y(acc, y, k);
   }
-  top_wait();
+  ws_top_wait();
   {
     float bq, iq;
     scales(nblk - 1, bq, iq);
@@ -1650,71 +1276,33 @@ __global__ __launch_bounds__(512) void k_gemm_wsy32(RowGemmArgs g) {
   const int tok = lane & 31, hh = lane >> 5;
   const int nb = (g.M + WP_R - 1) / WP_R;
   unsigned long long* const gran = reinterpret_cast<unsigned long long*>(g.pmax_out);
-  __shared__ int ticket;
-  if (tid == 0)
-    ticket = (int)atomicAdd(reinterpret_cast<unsigned*>(gran + 4L * 32 * nb), 1u);
-  __syncthreads();
-  const int q = ticket, wpt = gridDim.x >> 2;       // tickets as in k_gemm_wsx
-  const int t = (q >> 3) & 3, r0 = (q & 7) + 8 * (q >> 5);
+  int t, r0;
+  ws_assign_ticket(gran, nb, t, r0);
+  const int wpt = gridDim.x >> 2;
   if (r0 >= nb) return;
-  const int nblk = (nb - r0 + wpt - 1) / wpt;
+  const WsWalk wk(r0, wpt, nb);
+  const int nblk = wk.nblk;
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto rbk = [&](int k) { return r0 + min(k, nblk - 1) * wpt; };
-  auto dma4 = [](const float* gsrc, const float* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
+  auto rbk = [&](int k) { return wk.rb(k); };
   auto issue = [&](int k) {      // block k's A pieces 2w, 2w + 1 and its row scales
     uint8_t* st = lds + (k & 1) * WP_STAGE;
     const long row = min(rbk(k) * WP_R + tok, g.M - 1);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int s = 2 * wave + i;
-      dma16(g.A + kp_off(row, 32 * s + 16 * hh, WS_K), st + (s << 10));
+      lds_dma16(g.A + kp_off(row, 32 * s + 16 * hh, WS_K), st + (s << 10));
     }
-    dma4(g.sa + min(rbk(k) * WP_R + tok, g.M - 1), sal + ((k & 1) * 8 + wave) * 64);
+    lds_dma4(g.sa + min(rbk(k) * WP_R + tok, g.M - 1), sal + ((k & 1) * 8 + wave) * 64);
   };
   issue(0);
   v4i wr[W32_SR][2];
-  {
-    const int8_t* wsrc = g.W + ((long)(t * 8 + wave) << 15);
-    const v4i* ws = reinterpret_cast<const v4i*>(wsrc) + lane;
-#pragma unroll
-    for (int s = 0; s < W32_SR; ++s)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) wr[s][u] = ws[(s * 2 + u) * 64];
-#pragma unroll
-    for (int p = 0; p < (16 - W32_SR) * 2; ++p)
-      dma16(wsrc + ((W32_SR * 2 + p) << 10) + lane * 16, wl + ((wave * (16 - W32_SR) * 2 + p) << 10));
-    if (wave < 4) {
-      const int c = 128 * wave + 2 * lane;
-      *reinterpret_cast<float2*>(swl + c) = *reinterpret_cast<const float2*>(g.sw + 512 * t + c);
-      *reinterpret_cast<float2*>(swl + 512 + c) = *reinterpret_cast<const float2*>(g.bias + 512 * t + c);
-    }
-#pragma unroll
-    for (int s = 0; s < W32_SR; ++s)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) asm volatile("" ::"v"(wr[s][u]));
-  }
+  ws_load_w(wr, wl, g, t, wave, lane);
+  ws_fill_sw(swl, g, t, wave, lane);
+  ws_hold_w(wr);
   const int c0 = 512 * t + 64 * wave + 16 * hh;   // + 32 u: the lane's first column of tile u
   const __amdgpu_buffer_rsrc_t orsrc = ws_rsrc(g.out8, (long)(g.M + (g.M & 1)) * g.ldo8);
   const __amdgpu_buffer_rsrc_t srsrc = ws_rsrc(g.os, t == 0 ? 4L * g.M : 0L);
-  auto redb = [&](int k) { return red0 + (k & 1) * 8 * WP_R; };
-  auto dummy_stores = [&]() {
-    const __amdgpu_buffer_rsrc_t nul = ws_rsrc(g.out8, 0L);
-#pragma unroll
-    for (int d2 = 0; d2 < 3; ++d2) __builtin_amdgcn_raw_buffer_store_b32(0u, nul, 0, 0, 0);
-  };
+  auto redb = [&](int k) { return ws_redb(red0, k); };
   auto form_y = [&](v16i (&acc)[2], float (&y)[2][16], int k) {
     const float sr = sal[((k & 1) * 8 + wave) * 64 + lane];
     float am = 0.0f;
@@ -1735,44 +1323,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsy32(RowGemmArgs g) {
     am = fmaxf(am, __shfl_xor(am, 32));
     if (lane < 32) redb(k)[wave * WP_R + lane] = am;
   };
-  auto slice_max = [&](int k) {
-    const float* red = redb(k);
-    float m = red[tok];
-#pragma unroll
-    for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w * WP_R + tok]);
-    return m;
-  };
-  auto gidx = [&](int rb, int tt) { return ((long)rb * 4 + tt) * 32 + tok; };
-  auto publish = [&](int k, float m) {
-    if (wave == 0 && lane < 32 && t != g.drop_slice)
-      __hip_atomic_store(gran + gidx(rbk(k), t), (1ull << 32) | __float_as_uint(m),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  const unsigned lim = (unsigned)g.spin_limit;
-  auto full_max = [&](int k, float mloc) {
-    const int rb = rbk(k);
-    float m = mloc;
-    for (unsigned spin = 0;; ++spin) {
-      bool ok = true;
-      float mx = mloc;
-#pragma unroll
-      for (int d = 1; d < 4; ++d) {
-        const unsigned long long v = __hip_atomic_load(gran + gidx(rb, (t + d) & 3), __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT);
-        ok &= (v >> 32) == 1ull;
-        mx = fmaxf(mx, __uint_as_float((unsigned)v));
-      }
-      if (__all(ok)) { m = mx; break; }
-      if (spin >= lim) {                            // bounded: never hang, never silent
-        if (lane == 0)
-          __hip_atomic_fetch_or(g.status, DEV_E_EXCHANGE_TIMEOUT, __ATOMIC_RELAXED,
-                                __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(2);
-    }
-    return m;
-  };
+  const WsExchange ex{gran, g.status, (unsigned)g.spin_limit, t, g.drop_slice, tok};
   auto scales = [&](int k, float& bq, float& iq) {
     const float* gs = gsc + (k & 1) * 2 * WP_R;
     bq = gs[tok];
@@ -1833,7 +1384,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsy32(RowGemmArgs g) {
       }
     }
     mfma32_settle(acc);
-    if constexpr (!Q) dummy_stores();
+    if constexpr (!Q) ws_dummy_stores(g);
   };
   const std::true_type T_{};
   const std::false_type F_{};
@@ -1841,18 +1392,12 @@ __global__ __launch_bounds__(512) void k_gemm_wsy32(RowGemmArgs g) {
   v16i acc[2];
   float y0[2][16], y1[2][16];      // y of the even / odd blocks
   float mq0 = 0.0f, mq1 = 0.0f;    // their slice maxima
-  __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-  __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-  __builtin_amdgcn_s_barrier();
+  ws_top_wait();
   auto iter = [&](int k, float (&yb)[2][16], float& mb, float& mo) {
-    if (k > 0) {
-      __builtin_amdgcn_s_waitcnt(WAIT_VM(0));   // block k's DMA and the 3 stores after it (VM_CNT_ORDER)
-      __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-      __builtin_amdgcn_s_barrier();
-    }
+    if (k > 0) ws_top_wait();
     if (wave == 0 && k >= 1 && k <= nblk) {     // only wave 0 publishes and gathers
-      mo = slice_max(k - 1);
-      publish(k - 1, mo);
+      mo = ws_slice_max(redb(k - 1), tok);
+      if (lane < 32) ex.publish(rbk(k - 1), mo);
     }
     if (k + 1 < nblk) issue(k + 1);
     if (k < nblk) {
@@ -1862,10 +1407,10 @@ __global__ __launch_bounds__(512) void k_gemm_wsy32(RowGemmArgs g) {
     } else if (k >= 2) {
       quant_all(k - 2, yb);
     } else {
-      dummy_stores();
+      ws_dummy_stores(g);
     }
     if (wave == 0 && k >= 1 && k <= nblk) {
-      const float m = full_max(k - 1, mo);
+      const float m = ex.full_max(rbk(k - 1), mo);
       const float sc = fmaxf(m, 1e-5f) / 127.0f;
       const float inv = 1.0f / sc;
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sc), srsrc, 4 * (rbk(k - 1) * WP_R + tok), 0, 0);

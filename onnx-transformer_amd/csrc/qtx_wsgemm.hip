@@ -28,6 +28,13 @@
 // Epilogues (RowEpi, qtx_kernels.h): RE_QUANT (per-token quant over the 512-column slice),
 // RE_RES_LN (N = 512: residual + next LayerNorm + quant), RE_RELU_PMAX, RE_RELU_QUANT_PMAX.
 // Numerics: identical to k_gemm_row (the same canonical order; GPU == oracle bit for bit).
+// The kernels are schedules over the parts in qtx_ws.h (LDS-DMA, work assignment, resident-W
+// prologue, top wait, A issue, fragment fetches, y and its row maxima, the pinned MFMA block,
+// the exchange of slice maxima; DESIGN.md §4 "Anatomy of a weight-stationary kernel").  Where a
+// kernel writes one of them out instead, its assembly through the part differed in a resource
+// figure, an instruction-class count or inside the block loop (profiles/ws_share_isa.md).
+#include <type_traits>
+
 #include "qtx_ws.h"
 
 #include "qtx_knobs.h"
@@ -50,45 +57,37 @@ __global__ __launch_bounds__(512) void k_gemm_ws(RowGemmArgs g) {
   const int f = lane & 15, gq = lane >> 4;
   const int nsl = g.N >> 9;
   const int wpt = gridDim.x / nsl;               // workgroups per slice
-  const int t = blockIdx.x % nsl, r0 = blockIdx.x / nsl;
+  int t, r0;
+  ws_assign<0>(nsl, t, r0);
   const int nb = (g.M + WS_R - 1) / WS_R;
   if (r0 >= nb) return;
   QTX_STAMP(0);
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  // wave w moves K step w of the four row fragments (4 pieces of 8 KP lines)
+  // ws_issue<4, false> written out (64-row blocks: four row fragments per wave and K step), as
+  // are the W prologue, the top wait and the fragment fetches below: the only 64-row kernel,
+  // and through the shared parts its instances gain or lose a wait or change inside the block
+  // loop (profiles/ws_share_isa.md); as written all four compile to the parent's assembly
   auto issue = [&](uint8_t* st, int rb) {
     const int m0 = rb * WS_R;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const long row = min(m0 + 16 * i + f, g.M - 1);
-      dma16(g.A + kp_off(row, 64 * wave + 16 * gq, WS_K), st + ((wave * 4 + i) << 10));
+      lds_dma16(g.A + kp_off(row, 64 * wave + 16 * gq, WS_K), st + ((wave * 4 + i) << 10));
     }
   };
   issue(lds, r0);
-
-  // this wave's W fragments, resident for the whole launch: K steps 5-7 into LDS (12
-  // pieces, DMA), 0-4 into registers (K-step order: the first MFMAs wait only for the first
-  // loads)
+  // ws_load_w<true> and ws_hold_w (sw / bias are loaded per block)
   v4i wr[WS_SR][4];
   {
     const int8_t* wsrc = g.W + ((long)(t * 8 + wave) << 15);
 #pragma unroll
     for (int p = 0; p < (8 - WS_SR) * 4; ++p)
-      dma16(wsrc + ((WS_SR * 4 + p) << 10) + lane * 16, wl + ((wave * (8 - WS_SR) * 4 + p) << 10));
+      lds_dma16(wsrc + ((WS_SR * 4 + p) << 10) + lane * 16, wl + ((wave * (8 - WS_SR) * 4 + p) << 10));
     const v4i* ws = reinterpret_cast<const v4i*>(wsrc) + lane;
 #pragma unroll
     for (int s = 0; s < WS_SR; ++s)
 #pragma unroll
       for (int j = 0; j < 4; ++j) wr[s][j] = ws[(s * 4 + j) * 64];
-    // consume them here: otherwise the compiler's wait for them lands at the top of the
-    // block loop, where vmcnt(0) would also wait for the next block's DMA every iteration
 #pragma unroll
     for (int s = 0; s < WS_SR; ++s)
 #pragma unroll
@@ -101,10 +100,9 @@ __global__ __launch_bounds__(512) void k_gemm_ws(RowGemmArgs g) {
   for (int rb = r0; rb < nb; rb += wpt, ++it) {
     const int m0 = rb * WS_R;
     uint8_t* cur = lds + (NST == 2 ? (it & 1) * WS_STAGE : 0);
-    // this wave's DMA of the block retired, and with it the previous epilogue's stores:
-    // VM_CNT_ORDER (qtx_common.h) — a store issued after the DMA may retire before it, so a
-    // count that leaves the stores in flight could release the barrier early; the barrier
-    // makes every wave's part visible and frees the other stage / the epilogue areas
+    // ws_top_wait as asm statements (with the compiler-visible builtins RELU_PMAX loses a
+    // wait of the compiler's own later in the block); the barrier also frees the other stage
+    // and the epilogue areas
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -387,52 +385,20 @@ __global__ __launch_bounds__(512) void k_gemm_wsp(RowGemmArgs g) {
   const int f = lane & 15, gq = lane >> 4;
   const int nsl = g.N >> 9;
   const int wpt = gridDim.x / nsl;
-  const int t = blockIdx.x % nsl, r0 = blockIdx.x / nsl;
+  int t, r0;
+  ws_assign<0>(nsl, t, r0);
   const int nb = (g.M + WP_R - 1) / WP_R;
   if (r0 >= nb) return;
-  const int nblk = (nb - r0 + wpt - 1) / wpt;          // row blocks r0, r0 + wpt, ...
+  const WsWalk wk(r0, wpt, nb);
+  const int nblk = wk.nblk;
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  // block k of this workgroup (clamped: past the last one the last is re-loaded, never read,
-  // so every iteration issues the same DMAs); wave w moves K step w of the 2 row fragments
-  auto issue = [&](int k) {
-    const int rb = r0 + min(k, nblk - 1) * wpt;
-    uint8_t* st = lds + (k & 1) * WP_STAGE;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const long row = min(rb * WP_R + 16 * i + f, g.M - 1);
-      dma16(g.A + kp_off(row, 64 * wave + 16 * gq, WS_K), st + ((wave * 2 + i) << 10));
-    }
-  };
+  // block k's A (past the last block the last is re-loaded, never read)
+  auto issue = [&](int k) { ws_issue<2, false>(g, lds + (k & 1) * WP_STAGE, nullptr, wk.rb(k), wave, lane); };
   issue(0);
   v4i wr[SR][4];
-  {
-    const int8_t* wsrc = g.W + ((long)(t * 8 + wave) << 15);
-#pragma unroll
-    for (int p = 0; p < (8 - SR) * 4; ++p)
-      dma16(wsrc + ((SR * 4 + p) << 10) + lane * 16, wl + ((wave * (8 - SR) * 4 + p) << 10));
-    const v4i* ws = reinterpret_cast<const v4i*>(wsrc) + lane;
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) wr[s][j] = ws[(s * 4 + j) * 64];
-    // sw / bias of the slice into LDS (wave w: 128 floats)
-    if (wave < 4) {
-      const int c = 128 * wave + 2 * lane;
-      *reinterpret_cast<float2*>(swl + c) = *reinterpret_cast<const float2*>(g.sw + 512 * t + c);
-      *reinterpret_cast<float2*>(swl + 512 + c) = *reinterpret_cast<const float2*>(g.bias + 512 * t + c);
-    }
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(wr[s][j]));
-  }
+  ws_load_w<true>(wr, wl, g, t, wave, lane);
+  ws_fill_sw(swl, g, t, wave, lane);
+  ws_hold_w(wr);
   const int cs = 64 * wave + 16 * gq;            // the lane's 16 columns within the slice
   const int c0 = 512 * t + cs;
   // outputs: unconditional range-checked buffer stores (rows >= M dropped)
@@ -458,11 +424,9 @@ __global__ __launch_bounds__(512) void k_gemm_wsp(RowGemmArgs g) {
     for (int s = s0; s < s1; ++s) {
       v4i a[2], b[4];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const v4i*>(cur + ((s * 2 + i) << 10) + lane * 16);
+      for (int i = 0; i < 2; ++i) a[i] = ws_piece(cur, s * 2 + i, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        b[j] = s < SR ? wr[s < SR ? s : 0][j]
-                         : *reinterpret_cast<const v4i*>(wl + (((wave * (8 - SR) + s - SR) * 4 + j) << 10) + lane * 16);
+      for (int j = 0; j < 4; ++j) b[j] = ws_bfrag(wr, wl, wave, lane, s, j);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -510,9 +474,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsp(RowGemmArgs g) {
     if constexpr (EPI == RE_RELU_QUANT_PMAX) {
       m = fmaxf(fmaxf(pm[0], pm[1]), fmaxf(pm[2], pm[3]));   // pmax_n <= 4 (launch check)
     } else {
-      m = red[lane & 31];
-#pragma unroll
-      for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w * WP_R + (lane & 31)]);
+      m = ws_slice_max(red, lane & 31);
     }
     // rows m0 + (lane & 31); lanes 32-63 duplicate 0-31 and store the same values
     if constexpr (EPI == RE_RELU_PMAX) {
@@ -546,15 +508,6 @@ __global__ __launch_bounds__(512) void k_gemm_wsp(RowGemmArgs g) {
       }
     }
   };
-  auto top_wait = [&]() {
-    // the block's DMA retired, and the previous epilogue's stores with it (VM_CNT_ORDER,
-    // qtx_common.h: stores issued after the DMA may retire before it), then every wave's
-    // part visible (compiler-visible waits: its own wait insertion then knows what they
-    // retired)
-    __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-    __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-    __builtin_amdgcn_s_barrier();
-  };
   auto zero = [](v4i (&acc)[2][4]) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -567,9 +520,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsp(RowGemmArgs g) {
   const long long st_0 = QTX_NOW();
   v4i accp[2][4];
   float sap, pmp[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-  __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-  __builtin_amdgcn_s_barrier();
+  ws_top_wait();
   rowops(0, sap, pmp);
   issue(1);
   zero(accp);
@@ -579,7 +530,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsp(RowGemmArgs g) {
   const long long st_1 = QTX_NOW();
   for (int k = 1; k < nblk; ++k) {
     const long long t0 = QTX_NOW();
-    top_wait();
+    ws_top_wait();
     const long long t1 = QTX_NOW();
     st_top += t1 - t0;
     // last iteration's per-row loads complete HERE, before this iteration's loads and DMA:
@@ -622,7 +573,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsp(RowGemmArgs g) {
   }
   // ---- the last block's epilogue
   {
-    top_wait();
+    ws_top_wait();
     float y[2][16];
     epi1(accp, sap, y);
     __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
@@ -664,9 +615,11 @@ __global__ __launch_bounds__(512) void k_gemm_wsp(RowGemmArgs g) {
 // waits for the quantized output LAG places back (1: the one just before it), so the
 // quantization's dependent VALU chain need not finish before the next MFMA issues; 2 and 3
 // measured no faster (QKV 40.5 / 40.4 vs 40.0 us, FFN1 70.9 / 70.0 vs 68.1 us).
-// XG: the nsl column-slice workgroups of a row group on one XCD (blockIdx % 8 under
-// round-robin placement — speed only), dispatched together, so a row block's A is fetched
-// from HBM once and read from L2 by the other slices (0: slice = blockIdx % nsl)
+// XG: the slices of a row group on one XCD (ws_assign; 0: slice = blockIdx % nsl).
+// Parts (qtx_ws.h) in their plain order; ws_mfma_block carries the quantization one block
+// behind.  Written out here from lds_dma16 / lds_dma4: the A issue (through ws_issue the
+// address arithmetic at the top of the block loop is reordered) and the W prologue (through
+// ws_load_w / ws_fill_sw one ds_* and one s_waitcnt fewer) — profiles/ws_share_isa.md.
 template <int PRIO = 0, int LAG = 1, int XG = 1>
 __global__ __launch_bounds__(512) void k_gemm_wsq(RowGemmArgs g) {
   constexpr int SR = WS_SR, WL = 8 * (8 - SR) * 4 * 1024;
@@ -689,51 +642,23 @@ __global__ __launch_bounds__(512) void k_gemm_wsq(RowGemmArgs g) {
   }
   const int nsl = g.N >> 9;
   const int wpt = gridDim.x / nsl;
-  int t = blockIdx.x % nsl, r0 = blockIdx.x / nsl;
-  if (XG) {
-    // the first 8 * nsl * A workgroups: XCD x, slot j -> slice j % nsl of row group
-    // 8 * (j / nsl) + x; the rest (fewer than 8 * nsl) in blockIdx order after them
-    const int b = blockIdx.x, A = gridDim.x / (8 * nsl), aligned = 8 * nsl * A;
-    if (b < aligned) {
-      const int j = b >> 3;
-      t = j % nsl;
-      r0 = 8 * (j / nsl) + (b & 7);
-    } else {
-      t = (b - aligned) % nsl;
-      r0 = 8 * A + (b - aligned) / nsl;
-    }
-  }
+  int t, r0;
+  ws_assign<XG>(nsl, t, r0);
   const int nb = (g.M + WP_R - 1) / WP_R;
   if (r0 >= nb) return;
-  const int nblk = (nb - r0 + wpt - 1) / wpt;
+  const WsWalk wk(r0, wpt, nb);
+  const int nblk = wk.nblk;
   if (PRIO && wave >= 4) __builtin_amdgcn_s_setprio(1);
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto rbk = [&](int k) { return r0 + min(k, nblk - 1) * wpt; };
-  // block k's A rows and, per wave, its 32 row scales (lanes 32-63 repeat them) by LDS-DMA:
-  // no global load in the loop whose wait the compiler would count past the DMA (its
-  // counted vmcnt does not see the asm DMAs, so it would also wait for them)
-  auto dma4 = [](const float* gsrc, const float* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto issue = [&](int k) {
+  auto rbk = [&](int k) { return wk.rb(k); };
+  auto issue = [&](int k) {      // block k's A rows and its row scales
     uint8_t* st = lds + (k & 1) * WP_STAGE;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const long row = min(rbk(k) * WP_R + 16 * i + f, g.M - 1);
-      dma16(g.A + kp_off(row, 64 * wave + 16 * gq, WS_K), st + ((wave * 2 + i) << 10));
+      lds_dma16(g.A + kp_off(row, 64 * wave + 16 * gq, WS_K), st + ((wave * 2 + i) << 10));
     }
-    dma4(g.sa + min(rbk(k) * WP_R + (lane & 31), g.M - 1), sal + ((k & 1) * 8 + wave) * 64);
+    lds_dma4(g.sa + min(rbk(k) * WP_R + (lane & 31), g.M - 1), sal + ((k & 1) * 8 + wave) * 64);
   };
   issue(0);
   v4i wr[SR][4];
@@ -746,7 +671,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsq(RowGemmArgs g) {
       for (int j = 0; j < 4; ++j) wr[s][j] = ws[(s * 4 + j) * 64];
 #pragma unroll
     for (int p = 0; p < (8 - SR) * 4; ++p)
-      dma16(wsrc + ((SR * 4 + p) << 10) + lane * 16, wl + ((wave * (8 - SR) * 4 + p) << 10));
+      lds_dma16(wsrc + ((SR * 4 + p) << 10) + lane * 16, wl + ((wave * (8 - SR) * 4 + p) << 10));
     if (wave < 4) {
       const int c = 128 * wave + 2 * lane;
       *reinterpret_cast<float2*>(swl + c) = *reinterpret_cast<const float2*>(g.sw + 512 * t + c);
@@ -760,51 +685,20 @@ __global__ __launch_bounds__(512) void k_gemm_wsq(RowGemmArgs g) {
   const int cs = 64 * wave + 16 * gq;
   const __amdgpu_buffer_rsrc_t orsrc = ws_rsrc(g.out8 + (long)t * g.o8_ts, (long)g.M * g.ldo8);
   const __amdgpu_buffer_rsrc_t srsrc = ws_rsrc(g.os + (long)t * g.os_ts, 4L * g.M);
-  auto redb = [&](int k) { return red0 + (k & 1) * 8 * WP_R; };
-  auto top_wait = [&]() {
-    // the block's DMA retired, and the previous iteration's 3 stores per wave with it
-    // (VM_CNT_ORDER, qtx_common.h: a count leaving them in flight can release early)
-    __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-    __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-    __builtin_amdgcn_s_barrier();
-  };
-  // y of block k (acc, row scale sa) and the wave's partial row maxima into red[k & 1]
+  auto redb = [&](int k) { return ws_redb(red0, k); };
+  // y of block k (acc, its row scales) and the wave's partial row maxima into red[k & 1]
   auto form_y = [&](v4i (&acc)[2][4], float (&y)[2][16], int k) {
     float sr[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) sr[i] = sal[((k & 1) * 8 + wave) * 64 + 16 * i + f];
-    float am[2] = {0.0f, 0.0f};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float4 s4 = *reinterpret_cast<const float4*>(swl + cs + 4 * j);
-      const float4 b4 = *reinterpret_cast<const float4*>(swl + 512 + cs + 4 * j);
-      const float swj[4] = {s4.x, s4.y, s4.z, s4.w}, bj[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          y[i][4 * j + e] = ((float)acc[i][j][e] * sr[i]) * swj[e] + bj[e];
-          am[i] = fmaxf(am[i], fabsf(y[i][4 * j + e]));
-        }
-    }
-    float* red = redb(k);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      float a = am[i];
-      a = fmaxf(a, __shfl_xor(a, 16));
-      a = fmaxf(a, __shfl_xor(a, 32));
-      red[wave * WP_R + 16 * i + f] = a;
-    }
+    ws_form_y<false>(acc, sr, swl, redb(k), y, wave, lane);
   };
   // the scale of block k's rows (lane: row lane & 31) from red (stored), broadcast per
   // row fragment: divisor bq, reciprocal iq.  This chain sits before the block's first
   // pinned quantization (with constant scales QKV ran 38.2 vs 39.9 us): scale127 / rcp_cr
   // (the IEEE quotient and reciprocal, qtx_common.h) instead of two division sequences
   auto scales = [&](int k, float (&bq)[2], float (&iq)[2]) {
-    const float* red = redb(k);
-    float m = red[lane & 31];
-#pragma unroll
-    for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w * WP_R + (lane & 31)]);
+    const float m = ws_slice_max(redb(k), lane & 31);
     const float sc = scale127(fmaxf(m, 1e-5f));
     const float inv = rcp_cr(sc);
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sc), srsrc, 4 * (rbk(k) * WP_R + (lane & 31)), 0, 0);
@@ -818,50 +712,12 @@ __global__ __launch_bounds__(512) void k_gemm_wsq(RowGemmArgs g) {
     const long row = rbk(k) * WP_R + 16 * i + f;
     __builtin_amdgcn_raw_buffer_store_b128(v4u{d[0], d[1], d[2], d[3]}, orsrc, (int)(row * g.ldo8 + cs), 0, 0);
   };
-  // MFMAs of block k into acc; with q: the quantization of block k-1 (y) between them
+  auto cvt = [](float yv, float bq, float iq) { return rint_biased(div_cr(yv, bq, iq)); };
+  auto pack = [](float t0, float t1, float t2, float t3) { return pack4_biased(t0, t1, t2, t3); };
+  // MFMAs of block k into acc; with Q: the quantization of block k-1 (y) between them
   auto mfma_block = [&](v4i (&acc)[2][4], const uint8_t* cur, bool q, int kq, float (&y)[2][16]) {
-    float bq[2] = {0.0f, 0.0f}, iq[2] = {0.0f, 0.0f};
-    if (q) scales(kq, bq, iq);
-    float hist[3] = {0.0f, 0.0f, 0.0f}, tq[4];   // results of the last outputs, newest first
-    uint32_t d[4];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      v4i a[2], b[4];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const v4i*>(cur + ((s * 2 + i) << 10) + lane * 16);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        b[j] = s < SR ? wr[s < SR ? s : 0][j]
-                      : *reinterpret_cast<const v4i*>(wl + (((wave * (8 - SR) + s - SR) * 4 + j) << 10) + lane * 16);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = s * 8 + i * 4 + j;             // MFMA slot 0..63
-          if (!q || (n & 1) == 0) {
-            if (s == 0) mfma_asm<true>(acc[i][j], b[j], a[i]);
-            else mfma_asm<false>(acc[i][j], b[j], a[i]);
-          } else {
-            // quantized output o of block k-1: row fragment ii, column group jj, element e
-            const int o = n >> 1, ii = o >> 4, jj = (o >> 2) & 3, e = o & 3;
-            float yv = y[ii][4 * jj + e];
-            if (s == 0) mfma_pin<true>(acc[i][j], b[j], a[i], hist[LAG - 1], yv);
-            else mfma_pin<false>(acc[i][j], b[j], a[i], hist[LAG - 1], yv);
-            tq[e] = rint_biased(div_cr(yv, bq[ii], iq[ii]));
-            hist[2] = hist[1]; hist[1] = hist[0]; hist[0] = tq[e];
-            if (e == 3) {
-              d[jj] = pack4_biased(tq[0], tq[1], tq[2], tq[3]);
-              if (jj == 3) store_row(kq, ii, d);
-            }
-          }
-        }
-    }
-    mfma_settle(acc);
-    if (!q) {           // the 3 stores per iteration the next top wait counts (dropped)
-      const __amdgpu_buffer_rsrc_t nul = ws_rsrc(g.out8, 0L);
-#pragma unroll
-      for (int d2 = 0; d2 < 3; ++d2) __builtin_amdgcn_raw_buffer_store_b32(0u, nul, 0, 0, 0);
-    }
+    ws_mfma_block<LAG>(acc, wr, cur, wl, wave, lane, q, kq, y, scales, cvt, pack, store_row);
+    if (!q) ws_dummy_stores(g);   // the 3 stores per iteration the next top wait covers
   };
 
   v4i acc[2][4];
@@ -869,9 +725,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsq(RowGemmArgs g) {
   long long st_top = 0, st_mm = 0, st_y = 0;          // QTX_STAMPS builds only
   const long long st_0 = QTX_NOW(), rt_0 = QTX_RNOW();
   // ---- block 0: MFMAs, then its y
-  __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-  __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-  __builtin_amdgcn_s_barrier();
+  ws_top_wait();
   issue(1);
   mfma_block(acc, lds, false, 0, y);
   form_y(acc, y, 0);
@@ -879,7 +733,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsq(RowGemmArgs g) {
   // ---- block k: MFMAs with the quantization of block k-1, then the y of block k
   for (int k = 1; k < nblk; ++k) {
     const long long t0 = QTX_NOW();
-    top_wait();
+    ws_top_wait();
     const long long t1 = QTX_NOW();
     issue(k + 1);
     mfma_block(acc, lds + (k & 1) * WP_STAGE, true, k - 1, y);
@@ -904,7 +758,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsq(RowGemmArgs g) {
   }
 #endif
   // ---- the last block's quantization
-  top_wait();
+  ws_top_wait();
   {
     float bq[2], iq[2];
     scales(nblk - 1, bq, iq);
@@ -965,143 +819,44 @@ __global__ __launch_bounds__(512) void k_gemm_wsy(RowGemmArgs g) {
   const int f = lane & 15, gq = lane >> 4;
   const int nb = (g.M + WP_R - 1) / WP_R;
   unsigned long long* const gran = reinterpret_cast<unsigned long long*>(g.pmax_out);
-  __shared__ int ticket;
-  if (tid == 0)
-    ticket = (int)atomicAdd(reinterpret_cast<unsigned*>(gran + 4L * 32 * nb), 1u);
-  __syncthreads();
-  const int q = ticket, wpt = gridDim.x >> 2;       // tickets as in k_gemm_wsx
-  const int t = (q >> 3) & 3, r0 = (q & 7) + 8 * (q >> 5);
-  if (r0 >= nb) return;
-  const int nblk = (nb - r0 + wpt - 1) / wpt;
+  int t, r0;
+  ws_assign_ticket(gran, nb, t, r0);
+  const int wpt = gridDim.x >> 2;
+  if (r0 >= nb) return;                         // the whole row group (all 4 slices) skips
+  const WsWalk wk(r0, wpt, nb);
+  const int nblk = wk.nblk;
   if (PRIO && wave >= 4) __builtin_amdgcn_s_setprio(1);
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto rbk = [&](int k) { return r0 + min(k, nblk - 1) * wpt; };
-  auto dma4 = [](const float* gsrc, const float* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto issue = [&](int k) {      // block k's A rows and its row scales (as k_gemm_wsq)
+  auto rbk = [&](int k) { return wk.rb(k); };
+  // ws_issue<2, true> written out as in k_gemm_wsq (through it: 2 VGPRs fewer, the block loop changes)
+  auto issue = [&](int k) {
     uint8_t* st = lds + (k & 1) * WP_STAGE;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const long row = min(rbk(k) * WP_R + 16 * i + f, g.M - 1);
-      dma16(g.A + kp_off(row, 64 * wave + 16 * gq, WS_K), st + ((wave * 2 + i) << 10));
+      lds_dma16(g.A + kp_off(row, 64 * wave + 16 * gq, WS_K), st + ((wave * 2 + i) << 10));
     }
-    dma4(g.sa + min(rbk(k) * WP_R + (lane & 31), g.M - 1), sal + ((k & 1) * 8 + wave) * 64);
+    lds_dma4(g.sa + min(rbk(k) * WP_R + (lane & 31), g.M - 1), sal + ((k & 1) * 8 + wave) * 64);
   };
   issue(0);
   v4i wr[SR][4];
-  {
-    const int8_t* wsrc = g.W + ((long)(t * 8 + wave) << 15);
-    const v4i* ws = reinterpret_cast<const v4i*>(wsrc) + lane;
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) wr[s][j] = ws[(s * 4 + j) * 64];
-#pragma unroll
-    for (int p = 0; p < (8 - SR) * 4; ++p)
-      dma16(wsrc + ((SR * 4 + p) << 10) + lane * 16, wl + ((wave * (8 - SR) * 4 + p) << 10));
-    if (wave < 4) {
-      const int c = 128 * wave + 2 * lane;
-      *reinterpret_cast<float2*>(swl + c) = *reinterpret_cast<const float2*>(g.sw + 512 * t + c);
-      *reinterpret_cast<float2*>(swl + 512 + c) = *reinterpret_cast<const float2*>(g.bias + 512 * t + c);
-    }
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(wr[s][j]));
-  }
+  ws_load_w(wr, wl, g, t, wave, lane);
+  ws_fill_sw(swl, g, t, wave, lane);
+  ws_hold_w(wr);
   const int cs = 64 * wave + 16 * gq;
   const int c0 = 512 * t + cs;
   const __amdgpu_buffer_rsrc_t orsrc = ws_rsrc(g.out8, (long)(g.M + (g.M & 1)) * g.ldo8);
   const __amdgpu_buffer_rsrc_t srsrc = ws_rsrc(g.os, t == 0 ? 4L * g.M : 0L);
-  auto redb = [&](int k) { return red0 + (k & 1) * 8 * WP_R; };
-  auto dummy_stores = [&]() {
-    const __amdgpu_buffer_rsrc_t nul = ws_rsrc(g.out8, 0L);
-#pragma unroll
-    for (int d2 = 0; d2 < 3; ++d2) __builtin_amdgcn_raw_buffer_store_b32(0u, nul, 0, 0, 0);
-  };
+  auto redb = [&](int k) { return ws_redb(red0, k); };
   // Y: y of block k (before the ReLU) from acc and the wave's partial ReLU'd row maxima
   // -> red[k & 1]
   auto form_y = [&](v4i (&acc)[2][4], float (&y)[2][16], int k) {
     float sr[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) sr[i] = sal[((k & 1) * 8 + wave) * 64 + 16 * i + f];
-    float am[2] = {0.0f, 0.0f};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float4 s4 = *reinterpret_cast<const float4*>(swl + cs + 4 * j);
-      const float4 b4 = *reinterpret_cast<const float4*>(swl + 512 + cs + 4 * j);
-      const float swj[4] = {s4.x, s4.y, s4.z, s4.w}, bj[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          // pre-ReLU y: the maximum from 0 is the ReLU'd row maximum, and the codes take the
-          // ReLU in their conversion (pack4_relu_u8)
-          y[i][4 * j + e] = ((float)acc[i][j][e] * sr[i]) * swj[e] + bj[e];
-          am[i] = fmaxf(am[i], y[i][4 * j + e]);
-        }
-    }
-    float* red = redb(k);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      float a = am[i];
-      a = fmaxf(a, __shfl_xor(a, 16));
-      a = fmaxf(a, __shfl_xor(a, 32));
-      red[wave * WP_R + 16 * i + f] = a;
-    }
+    ws_form_y<true>(acc, sr, swl, redb(k), y, wave, lane);
   };
-  auto slice_max = [&](int k) {
-    const float* red = redb(k);
-    float m = red[lane & 31];
-#pragma unroll
-    for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w * WP_R + (lane & 31)]);
-    return m;
-  };
-  auto gidx = [&](int rb, int tt) { return ((long)rb * 4 + tt) * 32 + (lane & 31); };
-  auto publish = [&](int k, float m) {
-    // (g.drop_slice: the test hook that withholds one slice's maxima so its partners' waits
-    // time out, QTX_WSX_DROP_SLICE; -1 in production)
-    if (wave == 0 && lane < 32 && t != g.drop_slice)
-      __hip_atomic_store(gran + gidx(rbk(k), t), (1ull << 32) | __float_as_uint(m),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  const unsigned lim = (unsigned)g.spin_limit;
-  auto full_max = [&](int k, float mloc) {
-    const int rb = rbk(k);
-    float m = mloc;
-    for (unsigned spin = 0;; ++spin) {
-      bool ok = true;
-      float mx = mloc;
-#pragma unroll
-      for (int d = 1; d < 4; ++d) {
-        const unsigned long long v = __hip_atomic_load(gran + gidx(rb, (t + d) & 3), __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT);
-        ok &= (v >> 32) == 1ull;
-        mx = fmaxf(mx, __uint_as_float((unsigned)v));
-      }
-      if (__all(ok)) { m = mx; break; }
-      if (spin >= lim) {                            // bounded: never hang, never silent
-        if (lane == 0)
-          __hip_atomic_fetch_or(g.status, DEV_E_EXCHANGE_TIMEOUT, __ATOMIC_RELAXED,
-                                __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(2);
-    }
-    return m;
-  };
+  const WsExchange ex{gran, g.status, (unsigned)g.spin_limit, t, g.drop_slice, lane & 31};
   // block k's scale from its full row maximum m (stored; lane: row lane & 31), broadcast per
   // row fragment: divisor bq, reciprocal iq
   // block k's row scales (s and RN(1/s), written by wave 0 before this iteration's
@@ -1131,47 +886,13 @@ __global__ __launch_bounds__(512) void k_gemm_wsy(RowGemmArgs g) {
       store_row(k, i, d);
     }
   };
-  // M(k) into acc; Q: block kq's quantization (y, full maximum m) pinned between the MFMAs
+  auto cvt = [](float yv, float bq, float iq) { return div_cr(yv, bq, iq); };   // ReLU: in the pack
+  auto pack = [](float t0, float t1, float t2, float t3) { return pack4_relu_u8(t0, t1, t2, t3); };
+  // M(k) into acc; Q: block kq's quantization (y, its row scales) pinned between the MFMAs
   auto mfma_block = [&](v4i (&acc)[2][4], int k, auto q_c, int kq, float (&y)[2][16]) {
     constexpr bool Q = decltype(q_c)::value;
-    const uint8_t* cur = lds + (k & 1) * WP_STAGE;
-    float bq[2] = {0.0f, 0.0f}, iq[2] = {0.0f, 0.0f};
-    if constexpr (Q) scales(kq, bq, iq);
-    float hist[3] = {0.0f, 0.0f, 0.0f}, tq[4];   // results of the last outputs, newest first
-    uint32_t d[4];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      v4i a[2], b[4];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const v4i*>(cur + ((s * 2 + i) << 10) + lane * 16);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        b[j] = s < SR ? wr[s < SR ? s : 0][j]
-                      : *reinterpret_cast<const v4i*>(wl + (((wave * (8 - SR) + s - SR) * 4 + j) << 10) + lane * 16);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = s * 8 + i * 4 + j;
-          if (!Q || (n & 1) == 0) {
-            if (s == 0) mfma_asm<true>(acc[i][j], b[j], a[i]);
-            else mfma_asm<false>(acc[i][j], b[j], a[i]);
-          } else {
-            const int o = n >> 1, ii = o >> 4, jj = (o >> 2) & 3, e = o & 3;
-            float yv = y[ii][4 * jj + e];
-            if (s == 0) mfma_pin<true>(acc[i][j], b[j], a[i], hist[LAG - 1], yv);
-            else mfma_pin<false>(acc[i][j], b[j], a[i], hist[LAG - 1], yv);
-            tq[e] = div_cr(yv, bq[ii], iq[ii]);
-            hist[2] = hist[1]; hist[1] = hist[0]; hist[0] = tq[e];
-            if (e == 3) {
-              d[jj] = pack4_relu_u8(tq[0], tq[1], tq[2], tq[3]);
-              if (jj == 3) store_row(kq, ii, d);
-            }
-          }
-        }
-    }
-    mfma_settle(acc);
-    if constexpr (!Q) dummy_stores();
+    ws_mfma_block<LAG>(acc, wr, lds + (k & 1) * WP_STAGE, wl, wave, lane, Q, kq, y, scales, cvt, pack, store_row);
+    if constexpr (!Q) ws_dummy_stores(g);
   };
   const std::true_type T_{};
   const std::false_type F_{};
@@ -1179,27 +900,21 @@ __global__ __launch_bounds__(512) void k_gemm_wsy(RowGemmArgs g) {
   v4i acc[2][4];
   float y0[2][16], y1[2][16];      // y of the even / odd blocks
   float mq0 = 0.0f, mq1 = 0.0f;    // their slice maxima
-  __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-  __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-  __builtin_amdgcn_s_barrier();
+  ws_top_wait();
   // iteration k; yb / mb: the buffers of blocks of k's parity (block k-2 in, block k out),
   // mo: the slice maximum of block k-1 (the other parity)
   long long st_top = 0, st_fm = 0, st_mm = 0, st_y = 0;   // QTX_STAMPS builds only
   const long long st_0 = QTX_NOW();
   auto iter = [&](int k, float (&yb)[2][16], float& mb, float& mo) {
     const long long t0 = QTX_NOW();
-    if (k > 0) {
-      __builtin_amdgcn_s_waitcnt(WAIT_VM(0));   // block k's DMA and the 3 stores after it (VM_CNT_ORDER)
-      __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-      __builtin_amdgcn_s_barrier();
-    }
+    if (k > 0) ws_top_wait();
     const long long t1 = QTX_NOW();
     // (block k-2's row scales: gathered by wave 0 at the end of iteration k-1 from the
     // maxima its partners published an iteration before that; read after the barrier)
     const long long t2 = QTX_NOW();
     if (wave == 0 && k >= 1 && k <= nblk) {     // only wave 0 publishes and gathers
-      mo = slice_max(k - 1);
-      publish(k - 1, mo);
+      mo = ws_slice_max(redb(k - 1), lane & 31);
+      if (lane < 32) ex.publish(rbk(k - 1), mo);
     }
     if (k + 1 < nblk) issue(k + 1);
     if (k < nblk) {
@@ -1216,7 +931,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsy(RowGemmArgs g) {
     } else if (k >= 2) {
       quant_all(k - 2, yb);
     } else {
-      dummy_stores();
+      ws_dummy_stores(g);
     }
     // wave 0 (a SIMD arbitration winner: it reaches the next barrier ~1,300 cycles before
     // the losers) gathers block k-1's partner maxima now, so the load latency hides in its
@@ -1225,7 +940,7 @@ __global__ __launch_bounds__(512) void k_gemm_wsy(RowGemmArgs g) {
     // next GEMM; RN(1/s) for div_cr) once, for every wave
     if (wave == 0 && k >= 1 && k <= nblk) {
       const long long tf0 = QTX_NOW();
-      const float m = full_max(k - 1, mo);
+      const float m = ex.full_max(rbk(k - 1), mo);
       const float sc = fmaxf(m, 1e-5f) / 127.0f;
       const float inv = 1.0f / sc;
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sc), srsrc, 4 * (rbk(k - 1) * WP_R + (lane & 31)), 0, 0);
@@ -1281,46 +996,16 @@ __global__ __launch_bounds__(512) void k_gemm_wsr(RowGemmArgs g) {
   const int r0 = blockIdx.x;
   const int nb = (g.M + WP_R - 1) / WP_R;
   if (r0 >= nb) return;
-  const int nblk = (nb - r0 + wpt - 1) / wpt;
+  const WsWalk wk(r0, wpt, nb);
+  const int nblk = wk.nblk;
 
-  auto dma16 = [](const int8_t* gsrc, const uint8_t* lds_dst) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  };
-  auto rbk = [&](int k) { return r0 + min(k, nblk - 1) * wpt; };
-  auto issue = [&](int k) {
-    uint8_t* st = lds + (k & 1) * WP_STAGE;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const long row = min(rbk(k) * WP_R + 16 * i + f, g.M - 1);
-      dma16(g.A + kp_off(row, 64 * wave + 16 * gq, WS_K), st + ((wave * 2 + i) << 10));
-    }
-  };
+  auto rbk = [&](int k) { return wk.rb(k); };
+  auto issue = [&](int k) { ws_issue<2, false>(g, lds + (k & 1) * WP_STAGE, nullptr, rbk(k), wave, lane); };
   issue(0);
   v4i wr[SR][4];
-  {
-    const int8_t* wsrc = g.W + ((long)wave << 15);
-    const v4i* ws = reinterpret_cast<const v4i*>(wsrc) + lane;
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) wr[s][j] = ws[(s * 4 + j) * 64];
-#pragma unroll
-    for (int p = 0; p < (8 - SR) * 4; ++p)
-      dma16(wsrc + ((SR * 4 + p) << 10) + lane * 16, wl + ((wave * (8 - SR) * 4 + p) << 10));
-    if (wave < 4) {
-      const int c = 128 * wave + 2 * lane;
-      *reinterpret_cast<float2*>(swl + c) = *reinterpret_cast<const float2*>(g.sw + c);
-      *reinterpret_cast<float2*>(swl + 512 + c) = *reinterpret_cast<const float2*>(g.bias + c);
-    }
-#pragma unroll
-    for (int s = 0; s < SR; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(wr[s][j]));
-  }
+  ws_load_w(wr, wl, g, 0, wave, lane);      // N = 512: one slice
+  ws_fill_sw(swl, g, 0, wave, lane);
+  ws_hold_w(wr);
   const int cs = 64 * wave + 16 * gq;
   float ga[2][4], gb[2][4];
   ln_params512(g.ln_a, g.ln_b, lane, ga, gb);
@@ -1328,17 +1013,9 @@ __global__ __launch_bounds__(512) void k_gemm_wsr(RowGemmArgs g) {
   const __amdgpu_buffer_rsrc_t qrsrc = ws_rsrc(g.lnq, (long)(g.M + (g.M & 1)) * 512);
   const __amdgpu_buffer_rsrc_t srsrc = ws_rsrc(g.lns, 4L * g.M);
 
-  __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-  __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-  __builtin_amdgcn_s_barrier();
+  ws_top_wait();
   for (int k = 0; k < nblk; ++k) {
-    if (k > 0) {
-      // block k's DMA retired, and block k-1's 20 stores (4 rounds x 5) with it
-      // (VM_CNT_ORDER, qtx_common.h)
-      __builtin_amdgcn_s_waitcnt(WAIT_VM(0));
-      __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
-      __builtin_amdgcn_s_barrier();
-    }
+    if (k > 0) ws_top_wait();     // behind the DMA: block k-1's 20 stores (4 rounds x 5)
     const int m0 = rbk(k) * WP_R;
     const float sa = g.sa[min(m0 + (lane & 31), g.M - 1)];
     // this wave's 4 residual rows (row 8r + wave of round r), before the next block's DMA
@@ -1361,11 +1038,9 @@ __global__ __launch_bounds__(512) void k_gemm_wsr(RowGemmArgs g) {
     for (int s = 0; s < 8; ++s) {
       v4i a[2], b[4];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const v4i*>(cur + ((s * 2 + i) << 10) + lane * 16);
+      for (int i = 0; i < 2; ++i) a[i] = ws_piece(cur, s * 2 + i, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        b[j] = s < SR ? wr[s < SR ? s : 0][j]
-                      : *reinterpret_cast<const v4i*>(wl + (((wave * (8 - SR) + s - SR) * 4 + j) << 10) + lane * 16);
+      for (int j = 0; j < 4; ++j) b[j] = ws_bfrag(wr, wl, wave, lane, s, j);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll

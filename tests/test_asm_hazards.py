@@ -93,11 +93,19 @@ __global__ void k_bad(const int* a, int* o, int n) {
 
 def test_ws_kernels_wait_vmcnt_zero():
     """VM_CNT_ORDER in the source: the weight-stationary product kernels store inside their
-    block loops, so their hand-written waits must be vmcnt(0) (the race fixed in round 3)."""
-    src = open(os.path.join(CSRC, "qtx_wsgemm.hip")).read()
-    code = "\n".join(l.split("//")[0] for l in src.splitlines())
-    assert not re.search(r"WAIT_VM\(\s*[1-9]", code), "counted WAIT_VM in a ws kernel"
-    assert not re.search(r"vmcnt\(\s*[1-9]", code), "counted vmcnt in a ws kernel"
+    block loops, so their hand-written waits must be vmcnt(0) (the race fixed in round 3).
+    The top-of-block wait they share (ws_top_wait) lives in qtx_ws.h: both files are read, and
+    the kernels must still wait through it or by a vmcnt(0) of their own."""
+    for f in ("qtx_wsgemm.hip", "qtx_ws.h"):
+        src = open(os.path.join(CSRC, f)).read()
+        code = "\n".join(l.split("//")[0] for l in src.splitlines())
+        assert not re.search(r"WAIT_VM\(\s*[1-9]", code), f"counted WAIT_VM in {f}"
+        assert not re.search(r"vmcnt\(\s*[1-9]", code), f"counted vmcnt in {f}"
+    hdr = open(os.path.join(CSRC, "qtx_ws.h")).read()
+    body = hdr[hdr.index("void ws_top_wait()"):]
+    body = body[:body.index("}")]
+    assert "s_waitcnt(WAIT_VM(0))" in body and "s_barrier" in body
+    assert "ws_top_wait()" in open(os.path.join(CSRC, "qtx_wsgemm.hip")).read()
 
 
 def test_product_sources_read_no_environment_per_launch():
