@@ -310,6 +310,75 @@ int32_t qtx_greedy_dfault_resume(const qtx_model* m, int32_t B, int32_t S, int32
                                  const qtx_fault* fault, int32_t fault_step,
                                  int32_t* changed_host, void* stream);
 
+/* ---- faults of the KV-cached decode itself: one step fault or one cache upset ----
+ * qtx_greedy_decode_dfault follows the campaign's loop, which recomputes the whole prefix at
+ * every step: its fault leaves no trace.  The engine here appends quantized K/V rows to a cache
+ * and never recomputes them; this entry answers for that machine.  The reference has no such
+ * memory: the contract is tests/kvfault_ref.py, a restatement of the oracle's KV-cached
+ * DecodeState.step that takes one fault, plus an upset of its caches; results are equal bit for
+ * bit.  Exactly one of fault / upset is given (HOST pointers).
+ *
+ * Step fault: one qtx_fault with module 1, at step i.  Steps 0 .. i-1 run golden; step i's
+ * CACHED run is computed with the fault; steps i+1 .. run KV-cached from whatever step i left
+ * in the caches and in ids.  So a fault on a K or V projection, or anywhere in a lower layer,
+ * stays in the rows every later step reads.  Coordinates are those of the step's own MatMuls,
+ * one row per sentence:
+ *   Linear targets (Q K V O CQ CO FFN1 FFN2): rows index the step's [B] tokens (INPUT* / OUTPUT:
+ *   row = b; WEIGHT*: row = out channel; the WEIGHT16 window runs over the [B] rows, the
+ *   INPUT16 window over columns).
+ *   Attention targets: the conventions above with Sq = 1 and Sk = i + 1 (self) or S (cross),
+ *   e.g. QK WEIGHT: row = b*Sk + j, col = h*64 + d.  A WEIGHT16 window (over query rows) that
+ *   does not contain row 0 is a fault without effect.  The cache keeps the golden code in every
+ *   attention WEIGHT case: the fault corrupts the operand of that one MatMul in flight.
+ *   QTX_LIN_CK / CV: applied to the one-time memory K/V projection before step 0 (rows
+ *   [B * S]); the corrupted cross cache serves every step; step must be 0.
+ *
+ * Cache upset: one stored bit flips after step i-1 and before step i, and stays.
+ *   cache  0 self K, 1 self V, 2 cross K, 3 cross V, of decoder layer `layer`
+ *   row    self: b*max_len + j with 0 <= j < i (a row already written, so i >= 1);
+ *          cross: b*S + j, any i >= 0
+ *   field  0: bit `bit` (0..7) of the int8 code at column col (0 .. d_model-1);
+ *          1: bit `bit` of the row's float32 scale, col = 0 — mantissa and sign only (bits
+ *          0..22 and 31): an exponent flip can take the scores out of float range, and the
+ *          decoder's non-finite rules are not pinned.
+ *   Every copy a step reads is hit (the fused step reads the cross values from a regrouped
+ *   copy).  Upsets do not depend on the weight width (4-bit models too); step faults need
+ *   8-bit weights.
+ *
+ * Outputs as qtx_greedy_decode_dfault: the scored form (top_ids and top_logp given) or the
+ * plain form (both NULL); rec_ids / rec_logp [B, 2, 2] (both or neither): the golden and the
+ * faulty top 2 of step i, the golden pair from one golden cached run of step i on the golden
+ * caches, made before the fault or the upset is applied (not run when no record is asked for).
+ * step >= max_len - 1: nothing runs at or after it — a golden decode, rec_* untouched, the
+ * coordinates not checked.
+ * Path selection as qtx_greedy_decode_dfault (and its captured graphs: the golden ranges end
+ * where the fault or upset takes effect); the faulty step itself is one eager step built from
+ * the FaultArgs-aware GEMM at M = B, the row quantizers, the step's own attention kernel and,
+ * for an attention target, a one-query recomputation of the affected (sentence, head).
+ * Refused before anything is launched: both or neither of fault / upset, fault kind NONE or
+ * module != 1, step < 0, any coordinate outside the step's shapes, j >= i, a scale bit 23..30,
+ * CK / CV at step != 0: QTX_E_INVALID; a step fault with 4-bit weights: QTX_E_UNSUPPORTED; a
+ * short workspace: QTX_E_WORKSPACE; B * tgt_vocab and B * max_len * d_model below 2^30.
+ * Writes exactly ids, top_ids, top_logp, rec_ids, rec_logp.  ws:
+ * qtx_greedy_kvfault_workspace_size bytes; a dfault resume header on it is dropped. */
+typedef struct {
+  int32_t cache;     /* 0 self K, 1 self V, 2 cross K, 3 cross V */
+  int32_t layer;
+  int32_t field;     /* 0 code, 1 scale */
+  int32_t bit;
+  int64_t row;
+  int32_t col;
+  int32_t reserved;
+} qtx_cache_upset;
+size_t qtx_greedy_kvfault_workspace_size(const qtx_model* m, int32_t B, int32_t S,
+                                         int32_t max_len);
+int32_t qtx_greedy_decode_kvfault(const qtx_model* m, const int64_t* src, const uint8_t* src_mask,
+                                  int32_t B, int32_t S, int32_t max_len, int64_t start,
+                                  int64_t* ids, int64_t* top_ids, float* top_logp,
+                                  int64_t* rec_ids, float* rec_logp, void* ws, size_t ws_bytes,
+                                  const qtx_fault* fault, const qtx_cache_upset* upset,
+                                  int32_t step, void* stream);
+
 /* ---- beam search with EOS stop ----
  * The reference has no beam search (its only decode is the fixed-length greedy loop above):
  * this entry cites generator.py:15 for the log-probabilities and nothing else.  The contract is

@@ -2163,6 +2163,320 @@ int32_t qtx_greedy_dfault_resume(const qtx_model* m, int32_t B, int32_t S, int32
 }  // extern "C"
 
 // =======================================================================================
+// Faults of the KV-cached decode itself: one step fault or one cache upset
+// (include/qtx.h: qtx_greedy_decode_kvfault)
+// =======================================================================================
+namespace {
+
+// The workspace: the scored decode's (a prefix, as DfaultWS) and the record.
+struct KvfaultWS {
+  GreedyWS g;
+  int64_t* rec_ids;     // [B, 2, 2]
+  float* rec_logp;
+};
+
+KvfaultWS carve_kvfault(Arena& ar, const qtx_config& c, int B, int S, int max_len) {
+  KvfaultWS w;
+  w.g = carve_greedy(ar, c, B, S, max_len, true);
+  w.g.no_fold = true;
+  w.rec_ids = ar.take<int64_t>((size_t)B * 4);
+  w.rec_logp = ar.take<float>((size_t)B * 4);
+  return w;
+}
+
+size_t kvfault_ws(const qtx_config& c, int B, int S, int max_len) {
+  Arena ar;
+  carve_kvfault(ar, c, B, S, max_len);
+  return align_up(ar.used);
+}
+
+bool kv_attn_target(int lin) {
+  return lin == QTX_LIN_QK || lin == QTX_LIN_PV || lin == QTX_LIN_CQK || lin == QTX_LIN_CPV;
+}
+
+// A step fault's coordinates against the step's own MatMuls: one query row per sentence,
+// Sk = step + 1 self keys or S cross keys (include/qtx.h).  Linear targets: check_fault with
+// one token row per sentence.
+int kvfault_check_fault(const qtx_model* m, const qtx_fault* f, int B, int S, int step) {
+  const qtx_config& c = m->cfg;
+  if (!kv_attn_target(f->linear)) {
+    if ((f->linear == QTX_LIN_CK || f->linear == QTX_LIN_CV) && step != 0)
+      return fail(QTX_E_INVALID, "a memory K/V projection fault belongs to step 0 (step %d)", step);
+    return check_fault(m, f, 1, B, 1, S);
+  }
+  if (f->kind < QTX_FAULT_INPUT || f->kind > QTX_FAULT_OUTPUT)
+    return fail(QTX_E_INVALID, "fault kind %d", f->kind);
+  if (f->layer < 0 || f->layer >= c.n_layers) return fail(QTX_E_INVALID, "fault layer %d", f->layer);
+  const bool cross = f->linear == QTX_LIN_CQK || f->linear == QTX_LIN_CPV;
+  const bool qk = f->linear == QTX_LIN_QK || f->linear == QTX_LIN_CQK;
+  const bool in_kind = f->kind == QTX_FAULT_INPUT || f->kind == QTX_FAULT_INPUT16;
+  const long sk = cross ? S : step + 1, H = c.n_heads;
+  if (f->kind != QTX_FAULT_OUTPUT && (f->bit < 0 || f->bit > 7))
+    return fail(QTX_E_INVALID, "fault bit %d", f->bit);
+  long nr, nc, wmax;
+  if (f->kind == QTX_FAULT_OUTPUT) { nr = B; nc = qk ? H * sk : H * 64; wmax = 0; }
+  else if (in_kind) { nr = B; nc = qk ? H * 64 : H * sk; wmax = qk ? sk : 64; }
+  else { nr = B * sk; nc = H * 64; wmax = 1L << 30; }   // a window past query row 0: no effect
+  if (f->row < 0 || f->row >= nr || f->col < 0 || f->col >= nc)
+    return fail(QTX_E_INVALID, "fault index (%ld, %ld) outside [%ld, %ld]", (long)f->row,
+                (long)f->col, nr, nc);
+  if ((f->kind == QTX_FAULT_INPUT16 || f->kind == QTX_FAULT_WEIGHT16) &&
+      (f->win_len < 1 || f->win_len > 16 || f->win_start < 0 || f->win_start + f->win_len > wmax))
+    return fail(QTX_E_INVALID, "fault window [%ld, +%d) outside %ld", (long)f->win_start,
+                f->win_len, wmax);
+  return QTX_OK;
+}
+
+// Where an upset lands: the code byte(s) or the scale word, as offsets checked against the
+// caches' extents here, on the host.
+struct UpsetAt { int8_t* c0; int8_t* c1; float* s; };
+int kvfault_upset_at(const qtx_config& c, GreedyWS& g, const qtx_cache_upset* u, int B, int S,
+                     int max_len, int step, bool fused, UpsetAt* at) {
+  const long D = c.d_model;
+  if (u->cache < 0 || u->cache > 3) return fail(QTX_E_INVALID, "upset cache %d", u->cache);
+  if (u->layer < 0 || u->layer >= c.n_layers) return fail(QTX_E_INVALID, "upset layer %d", u->layer);
+  if (u->field != 0 && u->field != 1) return fail(QTX_E_INVALID, "upset field %d", u->field);
+  const bool self = u->cache < 2, is_v = u->cache & 1;
+  const long per = self ? max_len : S;            // rows per sentence
+  if (u->row < 0 || u->row >= (long)B * per)
+    return fail(QTX_E_INVALID, "upset row %ld outside [0, %ld)", (long)u->row, (long)B * per);
+  const long b = u->row / per, j = u->row % per;
+  if (self && j >= step)
+    return fail(QTX_E_INVALID, "upset of self-cache position %ld at step %d: not written yet", j, step);
+  if (u->field == 0 ? (u->bit < 0 || u->bit > 7) : !((u->bit >= 0 && u->bit <= 22) || u->bit == 31))
+    return fail(QTX_E_INVALID, "upset bit %d (codes: 0..7; scales: 0..22 and 31)", u->bit);
+  if (u->col < 0 || u->col >= (u->field == 0 ? D : 1))
+    return fail(QTX_E_INVALID, "upset col %d", u->col);
+  if (!at) return QTX_OK;
+  const int l = u->layer;
+  *at = UpsetAt{nullptr, nullptr, nullptr};
+  if (u->field == 1) {
+    float* sc = self ? (is_v ? g.svc[l] : g.skc[l]) : (is_v ? g.cross.sv[l] : g.cross.sk[l]);
+    at->s = sc + u->row;
+    return QTX_OK;
+  }
+  const long rm = u->row * D + u->col;                                   // row-major
+  const long G4 = (per + 3) / 4;
+  const long grp = ((b * G4 + j / 4) * D + u->col) * 4 + j % 4;          // 4-key groups
+  if (rm >= (long)B * per * D || grp >= (long)B * G4 * 4 * D) return fail(QTX_E_INVALID, "upset offset");
+  if (!is_v) at->c0 = (self ? g.kc[l] : g.cross.k8[l]) + rm;
+  else if (self) at->c0 = g.vc[l] + (fused ? grp : rm);                  // one layout per path
+  else {
+    at->c0 = g.cross.v8[l] + rm;                                         // every copy a step reads
+    if (fused) at->c1 = g.cvg[l] + grp;
+  }
+  return QTX_OK;
+}
+
+// Step `t` of the KV-cached decode with fault f, eager, on the whole batch: the decoder input
+// is tgt_embed(ids[:, t]); every layer's cache row t is (re)written from this run; the step's
+// logits land in g.logits.  Built from pieces that agree bit for bit with the fused step's
+// kernels: the FaultArgs-aware linear() at M = B, the row quantizers, and — on the fused
+// workspace, whose values lie in 4-key groups — k_dec_attn itself for the attention.
+int kvfault_step(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, int t,
+                 const qtx_fault* f, bool fused, hipStream_t st) {
+  const qtx_config& c = m->cfg;
+  const int D = c.d_model;
+  Scratch& s = g.dec;
+  HIPCHK(launch_set_steps(g.step, g.gsteps, 0, t, st));
+  HIPCHK(launch_embed(g.ids + t, max_len, B, 1, nullptr, t, m->tgt_lut, c.tgt_vocab, m->pe,
+                      c.max_len, s.x, D, st));
+  // the one query row of sentence af.b with the caches as the fused step keeps them
+  auto fused_attn_fault = [&](const AttnFault& af, int l, bool cross) -> int {
+    RC(quant(s.y, cross ? D : 3 * D, B, D, s.q8, s.sq, st));   // the query codes k_dec_attn formed
+    const long rows = cross ? S : max_len;
+    AttnArgs a{};
+    a.q = s.q8; a.q_bs = D; a.q_ld = D; a.sq = s.sq; a.sq_bs = 1;
+    a.k = cross ? g.cross.k8[l] : g.kc[l]; a.k_bs = rows * D; a.k_ld = D;
+    a.sk = cross ? g.cross.sk[l] : g.skc[l]; a.sk_bs = rows;
+    a.v = cross ? g.cvg[l] : g.vc[l];
+    a.sv = cross ? g.cross.sv[l] : g.svc[l]; a.sv_bs = rows;
+    if (cross) { a.mask = g.mask; a.m_bs = S; a.m_is = 0; }
+    a.ctx = s.ctx; a.c_bs = D; a.c_ld = D;
+    a.B = B; a.H = c.n_heads; a.Sq = 1; a.Sk = cross ? S : t + 1; a.dec = 1;
+    HIPCHK(launch_dec_attn_fault(a, af, (int)((rows + 3) / 4), st));
+    return QTX_OK;
+  };
+  for (int l = 0; l < c.n_layers; ++l) {
+    const DecLayer& L = m->dec[l];
+    auto fa = [&](GemmId gid) { return fault_for(f, 1, l, gid, B, c); };
+    // an attention WEIGHT16 window that misses the step's only query row has no effect
+    AttnFault af_self{}, af_cross{};
+    auto hits = [](AttnFault& af) {
+      if (af.row0 > 0 || af.row0 + af.nrows <= 0) return false;
+      af.row0 = 0; af.nrows = 1;
+      return true;
+    };
+    const bool self_f = attn_fault_for(f, 1, l, false, 1, t + 1, af_self) && hits(af_self);
+    const bool cross_f = attn_fault_for(f, 1, l, true, 1, S, af_cross) && hits(af_cross);
+    RC(ln_quant(s.x, B, L.ln[0], D, s.a8, s.sa, st));
+    RC(linear(c, L.qkv, s.a8, s.sa, B, 0, nullptr, s.y, 3 * D, st, fa(G_QKV)));
+    if (fused) {
+      DecAttnArgs at{};
+      at.y = s.y; at.ldy = 3 * D; at.kv_new = 1; at.step = g.step;
+      at.kc = g.kc[l]; at.vc = g.vc[l]; at.skc = g.skc[l]; at.svc = g.svc[l]; at.kv_bs = max_len;
+      at.ctx = s.ctx; at.B = B; at.host_step1 = t + 1;
+      HIPCHK(launch_dec_attn(at, B, st));
+      if (self_f) RC(fused_attn_fault(af_self, l, false));
+    } else {
+      RC(quant(s.y, 3 * D, B, D, s.q8, s.sq, st));
+      RowArgs kr = rows_quant(s.y + D, 3 * D, B, D, g.kc[l], g.skc[l]);
+      kr.rpb = 1; kr.dst_bstride = max_len; kr.dst_off = t;
+      HIPCHK(launch_rows(kr, st));
+      RowArgs vr = rows_quant(s.y + 2 * D, 3 * D, B, D, g.vc[l], g.svc[l]);
+      vr.rpb = 1; vr.dst_bstride = max_len; vr.dst_off = t;
+      HIPCHK(launch_rows(vr, st));
+      AttnArgs a = attn_args(s, B, 1, t + 1, max_len);
+      a.k = g.kc[l]; a.sk = g.skc[l]; a.v = g.vc[l]; a.sv = g.svc[l];
+      a.dec = 1;
+      HIPCHK(launch_attention(a, st));
+      if (self_f) HIPCHK(launch_attn_fault_rows(a, af_self, st));
+    }
+    RC(quant(s.ctx, D, B, D, s.a8, s.sa, st));
+    RC(linear(c, L.o, s.a8, s.sa, B, EPI_RESIDUAL, s.x, s.x, D, st, fa(G_O)));
+    if (fused) {
+      RC(ln_quant(s.x, B, L.ln[1], D, s.a8, s.sa, st));
+      RC(linear(c, L.cq, s.a8, s.sa, B, 0, nullptr, s.y, D, st, fa(G_CQ)));
+      DecAttnArgs at{};
+      at.y = s.y; at.ldy = D; at.kv_new = 0; at.S = S; at.mask = g.mask;
+      at.kc = g.cross.k8[l]; at.vc = g.cvg[l]; at.skc = g.cross.sk[l]; at.svc = g.cross.sv[l];
+      at.kv_bs = S; at.ctx = s.ctx; at.B = B;
+      HIPCHK(launch_dec_attn(at, B, st));
+      if (cross_f) RC(fused_attn_fault(af_cross, l, true));
+      RC(quant(s.ctx, D, B, D, s.a8, s.sa, st));
+      RC(linear(c, L.co, s.a8, s.sa, B, EPI_RESIDUAL, s.x, s.x, D, st, fa(G_CO)));
+    } else {
+      RC(cross_attn_block(m, L, l, s, g.cross, B, 1, S, g.mask, st, fa(G_CQ), fa(G_CO),
+                          cross_f ? &af_cross : nullptr));
+    }
+    RC(ffn_block(c, L.w1, L.w2, L.ln[2], s, B, st, fa(G_FFN1), fa(G_FFN2)));
+  }
+  RC(ln_out(s.x, B, m->dec_norm, D, g.xo, st));
+  HIPCHK(launch_generator_mfma(g.xo, D, B, nullptr, nullptr, m->gen_wt, m->gen_b, c.tgt_vocab,
+                               g.logits, st));
+  return QTX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t qtx_greedy_kvfault_workspace_size(const qtx_model* m, int32_t B, int32_t S,
+                                         int32_t max_len) {
+  if (!m || B <= 0 || S <= 0 || max_len < 1) return 0;
+  return kvfault_ws(m->cfg, B, S, max_len);
+}
+
+int32_t qtx_greedy_decode_kvfault(const qtx_model* m, const int64_t* src, const uint8_t* src_mask,
+                                  int32_t B, int32_t S, int32_t max_len, int64_t start,
+                                  int64_t* ids, int64_t* top_ids, float* top_logp,
+                                  int64_t* rec_ids, float* rec_logp, void* ws, size_t ws_bytes,
+                                  const qtx_fault* f, const qtx_cache_upset* u, int32_t step,
+                                  void* stream) {
+  if (!m || !src || !src_mask || !ids || !ws) return fail(QTX_E_INVALID, "null argument");
+  const bool scored = top_ids || top_logp;
+  if ((scored && (!top_ids || !top_logp)) || !rec_ids != !rec_logp)
+    return fail(QTX_E_INVALID, "top_ids / top_logp and rec_ids / rec_logp come in pairs");
+  if (!f == !u) return fail(QTX_E_INVALID, "exactly one of fault / upset");
+  const qtx_config& c = m->cfg;
+  RC(check_decode_shape(c, B, S, max_len));
+  if ((long)B * c.tgt_vocab >= (1L << 30) || (long)B * max_len * c.d_model >= (1L << 30))
+    return fail(QTX_E_INVALID, "B * tgt_vocab and B * max_len * d_model must be below 2^30");
+  if (f && (f->kind == QTX_FAULT_NONE || f->module != 1))
+    return fail(QTX_E_INVALID, "a step fault is one decoder fault (module 1)");
+  if (step < 0) return fail(QTX_E_INVALID, "step %d", step);
+  if (f && c.weight_bits != 8) return fail(QTX_E_UNSUPPORTED, "fault injection needs 8-bit weights");
+  if (knobs().dbg_tail) return fail(QTX_E_UNSUPPORTED, "kvfault decode: not with QTX_DBG_TAIL");
+  if ((scored || rec_ids) && c.tgt_vocab < 2)
+    return fail(QTX_E_INVALID, "top 2 needs tgt_vocab >= 2 (%d)", c.tgt_vocab);
+  if (ws_bytes < kvfault_ws(c, B, S, max_len)) return fail(QTX_E_WORKSPACE, "workspace too small");
+  const int last = max_len - 1;          // steps 0 .. last-1
+  const bool applied = step < last;      // else nothing runs at or after `step`: golden
+  const bool fused = greedy_fused(c, S, max_len);
+  Arena ar;
+  ar.base = (uint8_t*)ws; ar.cap = ws_bytes;
+  KvfaultWS w = carve_kvfault(ar, c, B, S, max_len);
+  GreedyWS& g = w.g;
+  UpsetAt at{};
+  if (applied && f) RC(kvfault_check_fault(m, f, B, S, step));
+  if (applied && u) RC(kvfault_upset_at(c, g, u, B, S, max_len, step, fused, &at));
+  hipStream_t st = (hipStream_t)stream;
+  dfault_forget(m, ws);
+  unsigned* cst = nullptr;
+  RC(call_status_begin(m, &cst, st));
+  g.enc.status = cst;
+  if (!scored) g.top_ids = nullptr, g.top_logp = nullptr;   // the plain step and its tail
+  const int V = c.tgt_vocab;
+  const bool rec = applied && rec_ids;
+  // the top 2 of the step that just ran, into rec[:, which, :]
+  auto record = [&](int which) -> int {
+    if (scored)
+      HIPCHK(launch_dfault_gold(g.top_ids, g.top_logp, last, step, B, w.rec_ids + 2 * which,
+                                w.rec_logp + 2 * which, st));
+    else
+      HIPCHK(launch_logsoftmax_top2(g.logits, B, V, nullptr, 0, nullptr, 0, w.rec_ids + 2 * which,
+                                    w.rec_logp + 2 * which, 2, st));
+    return QTX_OK;
+  };
+  // cached steps t0 .. last-1; with a record, step t0's top 2 is the faulty pair
+  auto run_from = [&](int t0) -> int {
+    if (rec) {
+      RC(dfault_steps(m, g, B, S, max_len, t0, t0 + 1, st));
+      RC(record(1));
+      ++t0;
+    }
+    return dfault_steps(m, g, B, S, max_len, t0, last, st);
+  };
+  HIPCHK(hipMemcpyAsync(g.mask, src_mask, (size_t)B * S, hipMemcpyDeviceToDevice, st));
+  RC(greedy_prologue(m, g, src, B, S, max_len, start, nullptr, fused, st));
+  if (!applied) {
+    RC(dfault_steps(m, g, B, S, max_len, 0, last, st));
+  } else {
+    // golden up to the step; with a record, the step itself once on the golden caches
+    RC(dfault_steps(m, g, B, S, max_len, 0, rec ? step + 1 : step, st));
+    if (rec) RC(record(0));
+    if (u) {
+      HIPCHK(launch_cache_upset(at.c0, at.c1, at.s, u->bit, st));
+      RC(run_from(step));
+    } else if (f->linear == QTX_LIN_CK || f->linear == QTX_LIN_CV) {
+      // the one-time memory K/V projection again, with the fault: it serves every step
+      RC(cross_kv(m, g.memory, B * S, g.cross, st, f));
+      if (fused) {
+        const long v_ls = c.n_layers > 1 ? (long)(g.cross.v8[1] - g.cross.v8[0]) : 0;
+        HIPCHK(launch_vgroup4(g.cross.v8[0], v_ls, c.n_layers, B, S, g.cvg[0],
+                              (long)B * ((S + 3) & ~3) * c.d_model, st));
+      }
+      RC(run_from(0));
+    } else {
+      RC(kvfault_step(m, g, B, S, max_len, step, f, fused, st));
+      if (scored || rec)
+        HIPCHK(launch_logsoftmax_top2(g.logits, B, V, nullptr, 0, nullptr, 0, w.rec_ids + 2,
+                                      w.rec_logp + 2, 2, st));
+      if (scored)
+        HIPCHK(launch_dfault_tail(w.rec_ids, w.rec_logp, B, step, max_len, g.ids, g.top_ids,
+                                  g.top_logp, nullptr, st));
+      else                   // the plain tail's rule (qtx_generator without log-probabilities)
+        HIPCHK(launch_logsoftmax_argmax(g.logits, B, V, nullptr, g.ids, max_len, nullptr, step + 1,
+                                        st));
+      RC(dfault_steps(m, g, B, S, max_len, step + 1, last, st));
+    }
+  }
+  HIPCHK(hipMemcpyAsync(ids, g.ids, (size_t)B * max_len * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+  if (scored && last > 0) {
+    const size_t nt = (size_t)B * last * 2;
+    HIPCHK(hipMemcpyAsync(top_ids, g.top_ids, nt * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(top_logp, g.top_logp, nt * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  if (rec) {
+    HIPCHK(hipMemcpyAsync(rec_ids, w.rec_ids, (size_t)B * 4 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(rec_logp, w.rec_logp, (size_t)B * 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  return QTX_OK;
+}
+
+}  // extern "C"
+
+// =======================================================================================
 // Beam-search decode with EOS stop (include/qtx.h: qtx_beam_decode)
 // =======================================================================================
 namespace {

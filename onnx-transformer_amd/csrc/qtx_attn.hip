@@ -631,12 +631,13 @@ namespace qtx {
 //                 for dims d in [lo, hi)
 //   AF_PV_WEIGHT  v[j0][d0] bit-flipped: the PV chain of dim d0 uses it for rows in [lo, hi)
 // =====================================================================================
-__global__ __launch_bounds__(64) void k_attn_fault_rows(AttnArgs a, AttnFault f) {
-  __shared__ float Ps[512];
-  __shared__ float Pf[512];
+// vload(b, j, c): the int8 value of key j of sentence b at model column c, wherever the
+// caller keeps it (row-major rows, or the decode step's 4-key groups).
+template <class VLoad>
+__device__ __forceinline__ void attn_fault_row(const AttnArgs& a, const AttnFault& f, int i,
+                                               float* Ps, float* Pf, VLoad&& vload) {
   const int lane = threadIdx.x;
   const int b = f.b, h = f.h, Sk = a.Sk;
-  const int i = f.row0 + blockIdx.x;                 // the query row of this wave
   const int hoff = 64 * h;
   const int8_t* qrow = a.q + b * a.q_bs + (long)i * a.q_ld + hoff;
   const float sqi = a.sq[b * a.sq_bs + i];
@@ -690,7 +691,7 @@ __global__ __launch_bounds__(64) void k_attn_fault_rows(AttnArgs a, AttnFault f)
   const bool pin = f.kind == AF_PV_INPUT && i == f.i && d >= f.lo && d < f.hi;
   const bool vw = f.kind == AF_PV_WEIGHT && d == f.d && i >= f.lo && i < f.hi;
   auto vint = [&](int j) {
-    const int8_t v8 = a.v[b * a.v_bs + (long)j * a.v_ld + hoff + d];
+    const int8_t v8 = vload(b, j, hoff + d);
     return (vw && j == f.j) ? flip(v8) : (int)v8;
   };
   float acc = 0.0f;
@@ -705,6 +706,28 @@ __global__ __launch_bounds__(64) void k_attn_fault_rows(AttnArgs a, AttnFault f)
   }
   if (f.kind == AF_PV_OUTPUT && i == f.i && d == f.d) acc = f.value;
   a.ctx[b * a.c_bs + (long)i * a.c_ld + hoff + d] = acc;
+}
+
+__global__ __launch_bounds__(64) void k_attn_fault_rows(AttnArgs a, AttnFault f) {
+  __shared__ float Ps[512];
+  __shared__ float Pf[512];
+  // one wave per affected query row
+  attn_fault_row(a, f, f.row0 + (int)blockIdx.x, Ps, Pf, [&](int b, int j, int c) {
+    return a.v[b * a.v_bs + (long)j * a.v_ld + c];
+  });
+}
+
+// k_dec_attn_fault: the Sq = 1 counterpart for the KV-cached step on the fused workspace
+// (qtx_greedy_decode_kvfault): the one query of sentence f.b against the caches as k_dec_attn
+// keeps them — keys row-major (a.k), values in 4-key groups of g4 groups per sentence (a.v:
+// byte ((b * g4 + j / 4) * 512 + c) * 4 + j % 4; a.v_bs / a.v_ld unused).  a.Sk keys: the
+// position + 1 (self) or S with the source mask (cross).  One wave.
+__global__ __launch_bounds__(64) void k_dec_attn_fault(AttnArgs a, AttnFault f, int g4) {
+  __shared__ float Ps[512];
+  __shared__ float Pf[512];
+  attn_fault_row(a, f, 0, Ps, Pf, [&](int b, int j, int c) {
+    return a.v[(((long)b * g4 + (j >> 2)) * 512 + c) * 4 + (j & 3)];
+  });
 }
 
 // =====================================================================================
@@ -779,6 +802,14 @@ __global__ __launch_bounds__(64) void k_attn_trace(AttnArgs a, float* qk, float*
 hipError_t launch_attn_trace(const AttnArgs& a, float* qk, float* pc, hipStream_t st) {
   if (a.Sk <= 0 || a.Sk > 512 || a.Sq <= 0 || a.B <= 0 || a.H <= 0) return hipErrorInvalidValue;
   k_attn_trace<<<dim3(a.Sq, a.B * a.H), dim3(64), 0, st>>>(a, qk, pc);
+  return hipGetLastError();
+}
+
+hipError_t launch_dec_attn_fault(const AttnArgs& a, const AttnFault& f, int g4, hipStream_t st) {
+  if (a.Sk <= 0 || a.Sk > 512 || a.Sq != 1 || f.b < 0 || f.b >= a.B || f.h < 0 || f.h >= a.H ||
+      f.i != 0 || g4 < (a.Sk + 3) / 4 || !a.dec)
+    return hipErrorInvalidValue;
+  k_dec_attn_fault<<<dim3(1), dim3(64), 0, st>>>(a, f, g4);
   return hipGetLastError();
 }
 

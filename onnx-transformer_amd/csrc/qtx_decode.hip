@@ -1931,6 +1931,27 @@ hipError_t launch_set_steps(int* step, int* gsteps, int G, int value, hipStream_
   return hipGetLastError();
 }
 
+// k_cache_upset: one stored bit of the decode's K/V caches flipped (qtx_greedy_decode_kvfault,
+// include/qtx.h qtx_cache_upset): bit `bit` of the code bytes c0 and c1 (c1: a second copy of
+// the same cell, e.g. the cross values' 4-key groups next to their row-major rows) or of the
+// float32 scale word s; each may be null.  The caller bounds every address on the host.
+__global__ __launch_bounds__(64) void k_cache_upset(int bit, uint8_t* c0, uint8_t* c1,
+                                                    uint32_t* s) {
+  if (threadIdx.x != 0) return;
+  if (c0) *c0 = (uint8_t)(*c0 ^ (1u << bit));
+  if (c1) *c1 = (uint8_t)(*c1 ^ (1u << bit));
+  if (s) *s = *s ^ (1u << bit);
+}
+
+hipError_t launch_cache_upset(int8_t* c0, int8_t* c1, float* s, int bit, hipStream_t st) {
+  if (bit < 0 || bit > ((c0 || c1) ? 7 : 31) || ((c0 || c1) && s) || (!c0 && !c1 && !s))
+    return hipErrorInvalidValue;
+  k_cache_upset<<<dim3(1), dim3(64), 0, st>>>(bit, reinterpret_cast<uint8_t*>(c0),
+                                             reinterpret_cast<uint8_t*>(c1),
+                                             reinterpret_cast<uint32_t*>(s));
+  return hipGetLastError();
+}
+
 
 // =====================================================================================
 // Beam search (include/qtx.h, beam search; qtx_api.hip beam_prologue / beam_steps /

@@ -144,6 +144,9 @@ struct AttnFault {
   float value;
 };
 hipError_t launch_attn_fault_rows(const AttnArgs& a, const AttnFault& f, hipStream_t st);
+// The same for the one query of a KV-cached step whose values lie in DecAttnArgs::vc's 4-key
+// groups (k_dec_attn_fault): a.Sq == 1, a.dec, g4 = groups per sentence; a.v_bs / a.v_ld unused.
+hipError_t launch_dec_attn_fault(const AttnArgs& a, const AttnFault& f, int g4, hipStream_t st);
 // The attention MatMuls' intermediates (k_attn_trace, canonical order): QK^T accumulators
 // qk [B,H,Sq,Sk] (float of the exact int), P codes pc [B,H,Sq,Sk] (rint(P*127)), and ctx as
 // launch_attention; qk / pc may be null.  Sk <= 512.
@@ -283,6 +286,9 @@ hipError_t launch_dfault_tail(const int64_t* rec_ids, const float* rec_logp, int
                               int* changed, hipStream_t st);
 hipError_t launch_causal_mask(uint8_t* mask, int T, hipStream_t st);
 hipError_t launch_set_steps(int* step, int* gsteps, int G, int value, hipStream_t st);
+// One stored cache bit flipped (k_cache_upset): bit 0..7 of the code bytes c0 / c1 (two copies
+// of one cell; either may be null), or bit 0..31 of the scale s — codes or a scale, not both.
+hipError_t launch_cache_upset(int8_t* c0, int8_t* c1, float* s, int bit, hipStream_t st);
 // Beam search (csrc/qtx_decode.hip; semantics: include/qtx.h, beam search).  Rows r = b * K + k.
 //   select:  the tail of a beam step on logits [B*K][V]: per sentence the K best of the K * V
 //            candidates; rewrites score / fin / len [B*K] in place, writes parent [B*K], the

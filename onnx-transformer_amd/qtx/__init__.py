@@ -7,6 +7,8 @@ Public surface mirrors the reference's entry points:
   greedy_decode(model, src, src_mask, max_len, start_symbol)
   greedy_decode(..., return_scores=True) -> (ys, Scores)   ~ the campaign's torch.topk(prob, 2)
   decode_fault_sweep(model, src, src_mask, max_len, start_symbol, trials)   ~ a campaign's trials
+  greedy_decode_kvfault(model, src, src_mask, max_len, fault= | upset=, step=)   a fault of the
+                                               KV-cached decode itself (no reference counterpart)
   score_targets(model, src, src_mask, tgt) -> TargetScores   ~ EncoderDecoder.forward on a given
                                                                target + log_softmax
 """
@@ -16,9 +18,9 @@ from .weights import (BOS, DEFAULT_SEED, EOS, PAD, UNK, ModelConfig, load_checkp
 __all__ = ["BOS", "EOS", "PAD", "UNK", "DEFAULT_SEED", "ModelConfig", "load_checkpoint",
            "positional_table", "synthetic_state_dict", "tensor_order", "QtxModel",
            "InferenceSession", "run_module", "set_default_model", "greedy_decode",
-           "greedy_decode_fault", "decode_fault_sweep", "plan_sweep", "SweepStats", "Scores",
-           "FaultStepRecord", "make_src_mask", "score_targets", "rescore_beam", "TargetScores",
-           "lib"]
+           "greedy_decode_fault", "greedy_decode_kvfault", "decode_fault_sweep", "plan_sweep",
+           "SweepStats", "Scores", "FaultStepRecord", "make_src_mask", "score_targets",
+           "rescore_beam", "TargetScores", "lib"]
 
 
 def __getattr__(name):
@@ -29,9 +31,9 @@ def __getattr__(name):
     if name in ("InferenceSession", "run_module", "set_default_model"):
         from . import session
         return getattr(session, name)
-    if name in ("greedy_decode", "greedy_decode_fault", "decode_fault_sweep", "plan_sweep",
-                "SweepStats", "Scores", "FaultStepRecord", "make_src_mask", "score_targets",
-                "rescore_beam", "TargetScores"):
+    if name in ("greedy_decode", "greedy_decode_fault", "greedy_decode_kvfault",
+                "decode_fault_sweep", "plan_sweep", "SweepStats", "Scores", "FaultStepRecord",
+                "make_src_mask", "score_targets", "rescore_beam", "TargetScores"):
         from . import decode
         return getattr(decode, name)
     if name == "lib":

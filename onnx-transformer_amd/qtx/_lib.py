@@ -56,7 +56,14 @@ class Fault(C.Structure):
                 ("bit", I32), ("value", F32), ("reserved", I32)]
 
 
+class CacheUpset(C.Structure):
+    """struct qtx_cache_upset (include/qtx.h)."""
+    _fields_ = [("cache", I32), ("layer", I32), ("field", I32), ("bit", I32), ("row", I64),
+                ("col", I32), ("reserved", I32)]
+
+
 FP = C.POINTER(Fault)
+UP = C.POINTER(CacheUpset)
 
 # name -> (restype, argtypes); must match include/qtx.h
 SIGNATURES = {
@@ -103,6 +110,9 @@ SIGNATURES = {
                                        I32, P]),
     "qtx_greedy_dfault_resume": (I32, [P, I32, I32, I32, P, P, P, P, P, P, SZ, FP, I32,
                                        C.POINTER(I32), P]),
+    "qtx_greedy_kvfault_workspace_size": (SZ, [P, I32, I32, I32]),
+    "qtx_greedy_decode_kvfault": (I32, [P, P, P, I32, I32, I32, I64, P, P, P, P, P, P, SZ, FP,
+                                        UP, I32, P]),
     "qtx_beam_workspace_size": (SZ, [P, I32, I32, I32, I32]),
     "qtx_beam_decode": (I32, [P, P, P, I32, I32, I32, I32, I64, I64, I64, I32, P, P, P,
                               C.POINTER(I32), P, SZ, P]),

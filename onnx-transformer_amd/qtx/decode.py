@@ -316,6 +316,38 @@ def _decode_dfault_cached(model, srcd, md, max_len, start_symbol, fault, target_
     return ys.cpu().numpy(), Scores(top_ids.cpu().numpy(), top_logp.cpu().numpy(), record)
 
 
+def greedy_decode_kvfault(model: QtxModel, src, src_mask, max_len: int, start_symbol: int = 0,
+                          fault=None, upset=None, step: int = 0, return_scores: bool = False):
+    """Greedy decode with one fault of the KV-cached decode itself (qtx_greedy_decode_kvfault;
+    the contract is tests/kvfault_ref.py) — what the engine that appends K/V rows and never
+    recomputes them does, where greedy_decode_fault follows the campaign's full-prefix loop.
+    Exactly one of:
+      fault  a decoder qtx.fault.Fault computed into the cached run of step ``step``; its
+             coordinates are those of the step's own MatMuls (one row per sentence, self keys
+             0 .. step); whatever it leaves in the caches and in ys serves every later step.
+             CK / CV: the one-time memory K/V projection, step 0.
+      upset  a qtx.fault.CacheUpset: one stored bit of a K/V code or scale flips before step
+             ``step`` and stays.
+    src / src_mask as greedy_decode; returns ys int64 [B, max_len] (numpy), or with
+    return_scores=True (ys, Scores), Scores.fault_step holding the golden and the faulty top 2
+    of step ``step`` (None when step >= max_len - 1: nothing runs at or after it)."""
+    import torch
+    if (fault is None) == (upset is None):
+        raise ValueError("greedy_decode_kvfault takes exactly one of fault / upset")
+    src = np.ascontiguousarray(np.asarray(src), np.int64)
+    B, S = src.shape
+    srcd = torch.from_numpy(src).to(model.device)
+    md = to_u8_mask(src_mask, model.device).reshape(B, S)
+    out = model.greedy_kvfault(srcd, md, step, fault=fault, upset=upset, max_len=max_len,
+                               start=start_symbol, scores=return_scores)
+    model.check()
+    if not return_scores:
+        return out.cpu().numpy()
+    ys, top_ids, top_logp, rec_ids, rec_logp = out
+    record = _record(int(step), rec_ids, rec_logp) if 0 <= step < max_len - 1 else None
+    return ys.cpu().numpy(), Scores(top_ids.cpu().numpy(), top_logp.cpu().numpy(), record)
+
+
 @dataclasses.dataclass
 class SweepStats:
     """decode_fault_sweep's counts: trials in all; ``n_resumed`` whose fault changed a token,

@@ -86,6 +86,48 @@ class Fault:
         return dataclasses.asdict(self)
 
 
+CACHES = {"self_k": 0, "self_v": 1, "cross_k": 2, "cross_v": 3}
+FIELDS = {"code": 0, "scale": 1}
+
+
+@dataclasses.dataclass
+class CacheUpset:
+    """One stored bit of the decode's K/V caches flipped (qtx_cache_upset): decoder layer
+    ``layer``; row = b * max_len + j (self caches, a position j already written) or b * S + j
+    (cross caches); field "code": bit 0..7 of the int8 code at column ``col``; field "scale":
+    bit 0..22 or 31 of the row's float32 scale (col 0)."""
+    cache: str                 # self_k, self_v, cross_k, cross_v
+    layer: int
+    row: int
+    col: int = 0
+    bit: int = 0
+    field: str = "code"
+
+    def to_c(self) -> "_lib.CacheUpset":
+        return _lib.CacheUpset(CACHES[self.cache], int(self.layer), FIELDS[self.field],
+                               int(self.bit), int(self.row), int(self.col), 0)
+
+    def as_dict(self):
+        return dataclasses.asdict(self)
+
+
+SCALE_BITS = tuple(range(23)) + (31,)
+
+
+def random_cache_upset(rng, cache, n_layers, B, rows_per_sentence, live_rows, d_model=512,
+                       scale=False):
+    """Draw an upset uniformly over the live cells of one cache kind: a layer, a sentence, one
+    of its first ``live_rows`` rows (the positions written so far for a self cache, S for a
+    cross cache; rows_per_sentence = max_len or S is the row stride), then a column and a bit
+    of the code — or, scale=True, one of the scale's mantissa / sign bits."""
+    layer, b, j = int(rng.integers(n_layers)), int(rng.integers(B)), int(rng.integers(live_rows))
+    row = b * int(rows_per_sentence) + j
+    if scale:
+        return CacheUpset(cache, layer, row, 0, int(SCALE_BITS[int(rng.integers(len(SCALE_BITS)))]),
+                          "scale")
+    return CacheUpset(cache, layer, row, int(rng.integers(d_model)), int(rng.integers(8)), "code")
+
+
 def linear_shape(linear: str, d_model=512, d_ff=2048):
     """(N, K) of the target QuantLinear."""
     return (d_ff if linear == "FFN1" else d_model, d_ff if linear == "FFN2" else d_model)

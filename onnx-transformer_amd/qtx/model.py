@@ -288,6 +288,25 @@ class QtxModel:
         return ids, top_ids, top_logp, rec_ids, rec_logp, np.array(changed[:], np.int32)
 
     @_on_device
+    def greedy_kvfault(self, src, src_mask_u8, step: int, fault=None, upset=None,
+                       max_len: int = 72, start: int = 0, scores: bool = False):
+        """KV-cached greedy decode with one fault of the cached decode itself
+        (qtx_greedy_decode_kvfault): ``fault``, a decoder qtx.fault.Fault computed into step
+        ``step``'s cached run, or ``upset``, a qtx.fault.CacheUpset flipped in storage before
+        step ``step`` — exactly one.  Returns as greedy_dfault: ids, or with scores=True (ids,
+        top_ids, top_logp, rec_ids, rec_logp), the record meaningful when step < max_len-1."""
+        B, S = src.shape
+        ids, top_ids, top_logp, rec_ids, rec_logp = self._dfault_outputs(B, max_len, scores)
+        ws = self.workspace(_lib.lib().qtx_greedy_kvfault_workspace_size(self.handle, B, S, max_len))
+        _lib.call("qtx_greedy_decode_kvfault", self.handle, _ptr(src), _ptr(src_mask_u8), B, S,
+                  max_len, int(start), _ptr(ids), _ptr(top_ids), _ptr(top_logp), _ptr(rec_ids),
+                  _ptr(rec_logp), _ptr(ws), ws.numel(),
+                  C.byref(fault.to_c()) if fault is not None else None,
+                  C.byref(upset.to_c()) if upset is not None else None, int(step),
+                  _stream(self.device))
+        return (ids, top_ids, top_logp, rec_ids, rec_logp) if scores else ids
+
+    @_on_device
     def embed(self, ids, which: str = "src", pos0: int = 0):
         torch = _torch()
         B, T = ids.shape
