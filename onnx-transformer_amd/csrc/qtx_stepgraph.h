@@ -1,6 +1,6 @@
 // qtx_stepgraph.h — the step-graph runner: what turns "run these decode steps" into hipGraph
 // captures and replays for every driver of the KV-cached step (greedy, decoder-fault and beam
-// decodes, qtx_api.hip).  A driver hands over a typed key, a step callback and a plan; the
+// decodes: qtx_api.hip, qtx_fault.hip, qtx_search.hip).  A driver hands over a typed key, a step callback and a plan; the
 // runner owns the sub-batch streams, the fork / join events and the cache of captured graphs.
 // Host code only.  The caller serialises run() per model (qtx_model::mu) with the model's
 // device current.
@@ -14,15 +14,12 @@
 #include <vector>
 
 #include "../../include/qtx.h"
+#include "qtx_carve.h"   // QTX_MAX_GROUPS
 #include "qtx_knobs.h"
 
 namespace qtx {
 
-// The fused decode runs the batch as up to QTX_MAX_GROUPS independent sub-batches, each a
-// graph on its own stream (qtx_greedy_decode).
-constexpr int QTX_MAX_GROUPS = 4;
-
-// Records a failed HIP call as the thread's last error and returns QTX_E_HIP (qtx_api.hip).
+// Records a failed HIP call as the thread's last error and returns QTX_E_HIP (qtx_model.hip).
 int stepgraph_hip_error(const char* what, hipError_t e);
 
 #define SG_HIP(expr)                                                       \

@@ -14,12 +14,13 @@ CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 REPO = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "libqtx.so")
 SOURCES = ["qtx_kernels.hip", "qtx_decode.hip", "qtx_gemm.hip", "qtx_wsgemm.hip", "qtx_attn.hip",
-           "qtx_ffn.hip", "qtx_api.hip", "qtx_knobs.hip"]
+           "qtx_ffn.hip", "qtx_model.hip", "qtx_api.hip", "qtx_fault.hip", "qtx_search.hip",
+           "qtx_ops.hip", "qtx_knobs.hip"]
 # measured-negative kernel variants and their switches: compiled only into the diagnostic
 # library (build(extra=...) -> libqtx_diag.so, with -DQTX_DIAG), never into libqtx.so
 DIAG_SOURCES = ["diag/qtx_wsgemm_diag.hip"]   # csrc/diag/: outside the product sources
 HEADERS = ["qtx_common.h", "qtx_kernels.h", "qtx_ws.h", "qtx_knobs.h", "qtx_beam.h", "qtx_carve.h",
-           "qtx_stepgraph.h"]
+           "qtx_stepgraph.h", "qtx_host.h"]
 
 # -ffp-contract=off: every float op is a separate IEEE op (the numerics contract,
 # DESIGN.md §3); HIP keeps correctly rounded fp32 '/' and sqrtf by default.
