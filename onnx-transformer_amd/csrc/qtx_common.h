@@ -127,6 +127,50 @@ __device__ __forceinline__ void wave_max_n(float (&v)[R]) {
     v[j] = fmaxf(fmaxf(lane_f(v[j], 0), lane_f(v[j], 16)), fmaxf(lane_f(v[j], 32), lane_f(v[j], 48)));
 }
 
+// wave_absmax: wave_max for a row absmax.  PRECONDITION: every lane's input is >= +0 and not
+// NaN (the lane-local stage is fmaxf(0, |x| ...), which drops NaN).  For such floats the
+// order of the values is the unsigned-integer order of their bit patterns (+0 = 0 the
+// least, +inf = 0x7f800000 the greatest, denormals in between), so the cross-lane stage is
+// an integer maximum: one v_max_u32 with a DPP source per level, four readlanes and scalar
+// maxima — fmaxf costs a canonicalising v_max_f32 x, x per operand on top (its NaN
+// semantics), ~11 VALU more per reduction.  `floor` (>= +0, not NaN) joins the scalar
+// maximum: wave_absmax(v, f) == fmaxf(wave_max(v), f), bit for bit.
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_u32(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
+}
+__device__ __forceinline__ uint32_t lane_u32(uint32_t v, int l) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
+}
+__device__ __forceinline__ float wave_absmax(float f, float floor = 0.0f) {
+  uint32_t v = __float_as_uint(f);
+  v = max(v, dpp_u32<0xB1>(v));
+  v = max(v, dpp_u32<0x4E>(v));
+  v = max(v, dpp_u32<0x141>(v));
+  v = max(v, dpp_u32<0x140>(v));
+  return __uint_as_float(max(max(max(lane_u32(v, 0), lane_u32(v, 16)), max(lane_u32(v, 32), lane_u32(v, 48))),
+                             __float_as_uint(floor)));
+}
+// R of them level by level, as wave_max_n
+template <int R>
+__device__ __forceinline__ void wave_absmax_n(float (&f)[R], float floor = 0.0f) {
+  uint32_t v[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) v[j] = __float_as_uint(f[j]);
+#pragma unroll
+  for (int j = 0; j < R; ++j) v[j] = max(v[j], dpp_u32<0xB1>(v[j]));
+#pragma unroll
+  for (int j = 0; j < R; ++j) v[j] = max(v[j], dpp_u32<0x4E>(v[j]));
+#pragma unroll
+  for (int j = 0; j < R; ++j) v[j] = max(v[j], dpp_u32<0x141>(v[j]));
+#pragma unroll
+  for (int j = 0; j < R; ++j) v[j] = max(v[j], dpp_u32<0x140>(v[j]));
+#pragma unroll
+  for (int j = 0; j < R; ++j)
+    f[j] = __uint_as_float(max(max(max(lane_u32(v[j], 0), lane_u32(v[j], 16)), max(lane_u32(v[j], 32), lane_u32(v[j], 48))),
+                               __float_as_uint(floor)));
+}
+
 // The same trees restricted to each 16-lane DPP row: every lane of the row gets the row's
 // canonical sum / max (the first four levels of wave_sum).
 __device__ __forceinline__ float row16_sum(float v) {
@@ -372,6 +416,28 @@ __device__ __forceinline__ float quant_scale(float absmax, float qmax) {
   return div_const(fmaxf(absmax, 1e-5f), qmax);
 }
 __device__ __forceinline__ int quant_val(float x, float s) { return (int)rintf(x / s); }
+// quant_scale(a, 127) for a row absmax that already holds the 1e-5 floor — wave_absmax(v,
+// 1e-5f): a >= 1e-5, not NaN, wave-uniform.  div_const's range vote is then a < 2^60 alone,
+// one compare of the bit pattern (the compiler cannot see through the integer maximum that
+// a > 2^-60, and would test all of div_ok).
+__device__ __forceinline__ float absmax_scale127(float a) {
+  if (__builtin_expect(__float_as_uint(a) < 0x5d800000u, 1)) return div_cr(a, 127.0f, 1.0f / 127.0f);
+  return a / 127.0f;
+}
+// R of them behind one test, as div_const_n
+template <int R>
+__device__ __forceinline__ void absmax_scale127_n(float (&a)[R]) {
+  uint32_t mx = 0u;
+#pragma unroll
+  for (int j = 0; j < R; ++j) mx = max(mx, __float_as_uint(a[j]));
+  if (__builtin_expect(mx < 0x5d800000u, 1)) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) a[j] = div_cr(a[j], 127.0f, 1.0f / 127.0f);
+  } else {
+#pragma unroll
+    for (int j = 0; j < R; ++j) a[j] = a[j] / 127.0f;
+  }
+}
 // Branch-free short forms of the scale chain for a >= 1e-5 (a row's clamped absmax), each
 // equal to the IEEE operation on every such input — checked exhaustively on the GPU's own
 // v_rcp_f32 (tools/probe_scale_exact.hip, profiles/r04_scale_exact.log):
@@ -483,6 +549,26 @@ __device__ __forceinline__ int quant_one(float x, float s) {
   const bool near = fabsf((r - floorf(r)) - 0.5f) < 0x1p-13f;
   if (__builtin_expect(__ballot(near) != 0ull, 0)) r = x / s;
   return (int)rintf(r);
+}
+// R of them (value j by scale j) behind ONE near-tie vote: the true division for all R when
+// any lane of any of them is near a tie.  Away from a tie the reciprocal product and the
+// true quotient round to the same integer (above), so the codes are those of R quant_one
+// calls; the R chains interleave instead of each ending in its own branch.
+template <int R>
+__device__ __forceinline__ void quant_one_n(const float (&x)[R], const float (&s)[R], int (&q)[R]) {
+  float r[R];
+  bool near = false;
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    r[j] = x[j] * __builtin_amdgcn_rcpf(s[j]);
+    near |= fabsf((r[j] - floorf(r[j])) - 0.5f) < 0x1p-13f;
+  }
+  if (__builtin_expect(__ballot(near) != 0ull, 0)) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) r[j] = x[j] / s[j];
+  }
+#pragma unroll
+  for (int j = 0; j < R; ++j) q[j] = (int)rintf(r[j]);
 }
 
 // The decoder's PV order (oracle attention_pv dec) for one (query row, dim):
@@ -620,7 +706,8 @@ __device__ __forceinline__ void ln_rows512(float (&v)[R][2][4], const float* a, 
 // subtractions exact for |r| < 2^22) is r's distance to the nearest integer, and
 // |d| > 0.5 - 2^-13 is exactly quant_pack's |frac(r) - 0.5| < 2^-13; one v_max3 per two
 // values folds it (4.5 VALU per value with the rint, against 6).
-template <int R>
+// IMAX: the rows' cross-lane maxima by wave_absmax_n (the decode step's kernels).
+template <int R, bool IMAX = false>
 __device__ __forceinline__ void quant_rows512(const float (&v)[R][2][4], uint32_t (&q)[R][2],
                                               float (&sc)[R]) {
 #pragma unroll
@@ -631,10 +718,15 @@ __device__ __forceinline__ void quant_rows512(const float (&v)[R][2][4], uint32_
 #pragma unroll
       for (int e = 0; e < 4; ++e) sc[j] = fmaxf(sc[j], fabsf(v[j][c][e]));
   }
-  wave_max_n<R>(sc);
+  if constexpr (IMAX) {
+    wave_absmax_n<R>(sc, 1e-5f);                  // (sc >= +0, NaN dropped above)
+    absmax_scale127_n<R>(sc);
+  } else {
+    wave_max_n<R>(sc);
 #pragma unroll
-  for (int j = 0; j < R; ++j) sc[j] = fmaxf(sc[j], 1e-5f);
-  div_const_n<R>(sc, 127.0f);                     // quant_scale of each row
+    for (int j = 0; j < R; ++j) sc[j] = fmaxf(sc[j], 1e-5f);
+    div_const_n<R>(sc, 127.0f);                   // quant_scale of each row
+  }
   constexpr float BIAS = 12582912.0f;
   float t[R][8];
   float dm = 0.0f;

@@ -191,7 +191,7 @@ __device__ __forceinline__ void skinny_prologue(const SkinnyArgs& g, uint8_t* As
     }
 #else
     ln_rows512<RPW>(v, ga, gb);
-    quant_rows512<RPW>(v, q, sc);
+    quant_rows512<RPW, true>(v, q, sc);
 #endif
 #pragma unroll
     for (int j = 0; j < RPW; ++j) {
@@ -236,7 +236,11 @@ __device__ __forceinline__ void skinny_prologue(const SkinnyArgs& g, uint8_t* As
         } else {
           lm = fmaxf(pm[jb][0], pm[jb][1]);
         }
-        const float sc = quant_scale(wave_max(lm), 127.0f);
+        // (OWN: lm >= +0 and no NaN — wave_absmax, the 1e-5 floor of quant_scale inside
+        // it; the partial maxima come from memory, where a caller may have put NaN)
+        float sc;
+        if constexpr (OWN) sc = absmax_scale127(wave_absmax(lm, 1e-5f));
+        else sc = quant_scale(wave_max(lm), 127.0f);
         uint32_t* dst = reinterpret_cast<uint32_t*>(As + r * LDA);
         float tf[4 * NC];
 #pragma unroll
@@ -388,8 +392,10 @@ __global__ __launch_bounds__(256) void k_skinny(QTX_KA_PARAMS, SkTail kt) {
 // (16 values per lane: half the dependent quantization chain of k_skinny's one row per
 // wave), K split 8 ways (4 weight fragments per lane), exact int32 reduction over the 8
 // waves.  Rows per workgroup 4, 16 columns.  Bit-identical to k_skinny.
-// OWN (A_F32R): the row maximum from the row itself — each wave's half-row maximum, the two
-// halves met through LDS — instead of FFN1's per-tile partial maxima.
+// OWN (A_F32R): the row maximum from the row itself instead of FFN1's per-tile partial
+// maxima — each wave loads the row's other half as well (8 float4 loads issued together
+// instead of 4) and forms the whole row's maximum, so the two waves of a row agree on the
+// scale without meeting in LDS behind a barrier of the 8 waves.
 // =====================================================================================
 template <bool OWN>
 __global__ __launch_bounds__(512) void k_skinny8_ffn2(QTX_KA_PARAMS, SkTail kt) {
@@ -398,7 +404,6 @@ __global__ __launch_bounds__(512) void k_skinny8_ffn2(QTX_KA_PARAMS, SkTail kt) 
   __shared__ __attribute__((aligned(16))) uint8_t As[16 * LDA];
   __shared__ float sas[16];
   __shared__ v4i red[8][64];
-  __shared__ float hmax[8];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int fr = lane & 15, fg = lane >> 4;
   const int n0 = blockIdx.x * 16, m0 = blockIdx.y * RB;
@@ -410,9 +415,15 @@ __global__ __launch_bounds__(512) void k_skinny8_ffn2(QTX_KA_PARAMS, SkTail kt) 
   for (int c = 0; c < 4; ++c)
     t[c] = ld_at(reinterpret_cast<const float4*>(g.X), 4u * (unsigned)(m * (int)g.ldx + 4 * (lane + 64 * (4 * half + c))));
   float pm[2] = {0.0f, 0.0f};
-  if constexpr (!OWN)
+  float4 to[4] = {};   // OWN: the row's other half, for the row maximum alone
+  if constexpr (!OWN) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) pm[u] = ld_at(g.pmax_in, 4u * (unsigned)(min(lane + 64 * u, g.pmax_n - 1) * g.M + m));
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      to[c] = ld_at(reinterpret_cast<const float4*>(g.X), 4u * (unsigned)(m * (int)g.ldx + 4 * (lane + 64 * (4 * (half ^ 1) + c))));
+  }
   // 2. then this wave's weight fragments and (wave 0) the epilogue operands
   const int n = min(n0 + fr, g.N - 1);
   uint4 wf[NS];
@@ -429,20 +440,18 @@ __global__ __launch_bounds__(512) void k_skinny8_ffn2(QTX_KA_PARAMS, SkTail kt) 
   // 3. per-token quantization of the half row into LDS
   {
     const bool ok = m0 + r < g.M;
-    float rmax;
+    float sc;
     if constexpr (OWN) {
-      float lm = 0.0f;
+      float lm = 0.0f;     // (>= +0, NaN dropped: wave_absmax's precondition)
 #pragma unroll
-      for (int c = 0; c < 4; ++c)
+      for (int c = 0; c < 4; ++c) {
         lm = fmaxf(lm, fmaxf(fmaxf(fabsf(t[c].x), fabsf(t[c].y)), fmaxf(fabsf(t[c].z), fabsf(t[c].w))));
-      lm = wave_max(lm);
-      if (lane == 0) hmax[wave] = lm;
-      __syncthreads();
-      rmax = fmaxf(hmax[2 * r], hmax[2 * r + 1]);
+        lm = fmaxf(lm, fmaxf(fmaxf(fabsf(to[c].x), fabsf(to[c].y)), fmaxf(fabsf(to[c].z), fabsf(to[c].w))));
+      }
+      sc = absmax_scale127(wave_absmax(lm, 1e-5f));   // quant_scale, its 1e-5 floor in the maximum
     } else {
-      rmax = wave_max(fmaxf(pm[0], pm[1]));
+      sc = quant_scale(wave_max(fmaxf(pm[0], pm[1])), 127.0f);
     }
-    const float sc = quant_scale(rmax, 127.0f);
     float tf[16];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -778,15 +787,16 @@ hipError_t launch_skinny(const SkinnyArgs& g, int wbits, hipStream_t st) {
 // so with B % 8 == 0 they land on one XCD (workgroups go round-robin over the 8 XCDs).
 // The value cache is kept in groups of 4 keys (round 6): byte ((b * G4 + j / 4) * 512 + d) * 4
 // + j % 4 holds v[b][j][d] (G4 = ceil(kv_bs / 4)), so one dword is 4 consecutive keys of one
-// dim — the PV's 4-key step in one ds_read_b32 and 4 SDWA conversions instead of 4 byte
-// reads.
+// dim — the PV's 4-key step is one dword and 4 SDWA conversions, and the dword of (group,
+// dim = lane) is a coalesced load straight into the register the chain reads (round 10: the
+// value rows are not staged in LDS either).
 // =====================================================================================
 constexpr int DEC_MAXK = 128;
 
 // The lead blocks of k_dec_attn (kernel-argument preload, above): what the loads of phase 0
 // need.  Self: the device position counter (read only by a step replayed at several
 // positions, and by no load's address) stays in the tail; cross: the mask pointer does —
-// its bytes are the phase's last loads, issued when the tail has long arrived.
+// its bytes are loaded behind the key rows and scales, when the tail has long arrived.
 template <bool KV_NEW> struct DaLead;
 template <> struct DaLead<true> {
   uint64_t y; int ldy, kv_bs; uint64_t kc, vc, skc, svc; int host_step1, zero;
@@ -818,8 +828,6 @@ __device__ __forceinline__ DecAttnArgs da_args(const KaLead& k, const DaTail& t)
 template <bool KV_NEW, int NIT>
 __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
   const DecAttnArgs a = da_args<KV_NEW>(QTX_KA_VALS, kt);
-  // values of this head, 4-key groups: dword g * 64 + d = keys 4g .. 4g + 3 of dim d
-  __shared__ __attribute__((aligned(16))) uint8_t Vs[DEC_MAXK * 64];
   __shared__ __attribute__((aligned(16))) float PS[DEC_MAXK];   // RN(P_j * s_v[j]), 0 past Sk
   // this step's q codes and (self) k codes of the head: 64 B each, read back as MFMA fragments
   __shared__ __attribute__((aligned(16))) int8_t qs[KV_NEW ? 128 : 64];
@@ -830,7 +838,7 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
 
   // phase 0: every global load first (one memory latency): this step's q (k, v) rows
   // first — vmcnt retires in issue order, so their quantization (phase 1) then runs while
-  // the cached keys and values are in flight — then the key/value rows of this head (row r
+  // the cached keys and values are in flight — then the key rows of this head (row r
   // = 4 uint4; lane takes row 16*i + lane%16, chunk lane/16 — the B fragment of the int8
   // 16x16x64 MFMA for keys 16i .. 16i + 15, so the keys are never staged; the same 16 rows x
   // 64 B per load instruction as any other lane <-> (row, chunk) map; clamped: no divergent
@@ -854,23 +862,19 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
   const int nrows = KV_NEW ? (a.host_step1 > 0 ? a.host_step1 : (int)a.kv_bs) : a.S;
   const long kvb = (long)b * a.kv_bs;
   const long vgb = (long)b * ((a.kv_bs + 3) >> 2);     // the sentence's first value group
-  // values: per 16 keys, 4 groups x this head's 64 dims x 4 B = 1 KB, lane = group
-  // 4 i + lane / 16, dims 4 (lane % 16) .. + 3
-  const int vg = lane >> 4, vd = 4 * (lane & 15), glast = (nrows - 1) >> 2;
+  const int glast = (nrows - 1) >> 2;                  // the last staged 4-key value group
   // wave-uniform bases of this head's rows and 32-bit lane offsets: the loads take the
   // scalar-base + vector-offset form instead of 64-bit address arithmetic per load
   const int8_t* const kbase = a.kc + kvb * 512 + h * 64;
   const int8_t* const vbase = a.vc + vgb * 2048 + h * 256;
-  uint4 kr[NIT], vr[NIT];
+  uint4 kr[NIT];
 #pragma unroll
   for (int i = 0; i < NIT; ++i) {
     const unsigned koff = (unsigned)(min(16 * i + fr, nrows - 1) * 512 + 16 * fg);
-    const unsigned voff = (unsigned)(min(4 * i + vg, glast) * 2048 + 4 * vd);
     // non-temporal: each K/V row is read once per step by one wave, so it should not push
     // the weights (re-read every step) out of the XCD's L2 (B = 256: 36.2 -> 35.1 ms; the
     // default policy re-measured in round 6: B = 32 12.87 vs 12.84, B = 256 26.25 vs 25.58 ms)
     kr[i] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const v4i*>(kbase + koff)));
-    vr[i] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const v4i*>(vbase + voff)));
   }
   const int j0 = min(lane, nrows - 1), j1 = min(lane + 64, nrows - 1);
   const float* const skb = a.skc + kvb;
@@ -883,6 +887,24 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
     keep0 = mb[(unsigned)j0] != 0;
     keep1 = mb[(unsigned)j1] != 0;
   }
+  // the value rows straight into the registers the PV chains read (phase 4), never staged
+  // in LDS: in the 4-key group layout the dword of group 4 g + q and dim = lane is vg4[g][q],
+  // one coalesced 256-byte load per group.  Issued last (the barrier keeps the scheduler from
+  // moving them ahead of a key row), so no wait ahead of the PV phase includes them.
+  // Non-temporal as the key rows.  The groups are clamped to the last staged one (wave-
+  // uniform): in the last fragment each group; a fragment ahead of it lies wholly inside the
+  // staged rows (NIT = ceil(nrows / 16), dec_attn_nit: NIT >= 2 means nrows > 16, glast >= 4),
+  // so its four groups share one clamp — the identity — and sit at constant offsets from it.
+  uint32_t vg4[NIT][4];
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int g = 0; g < NIT; ++g)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int grp = g < NIT - 1 ? min(4 * g, max(glast - 3, 0)) + q : min(4 * g + q, glast);
+      vg4[g][q] = __builtin_nontemporal_load(
+          reinterpret_cast<const uint32_t*>(vbase + (unsigned)(grp * 2048 + 4 * lane)));
+    }
   // the position (no load's address depends on it: read after they are issued; the counter's
   // pointer comes with the trailing arguments).  Clamped: a stale position (a counter not
   // reset) must not index past the cache
@@ -898,22 +920,38 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
   }
 
   // phase 1: per-token scales of q (and k, v) over the full 512-wide rows
-  auto amax8 = [](const float4 (&v)[2]) {
+  // (the lane's |x| maximum: >= +0, NaN dropped — wave_absmax's precondition)
+  auto lmax8 = [](const float4 (&v)[2]) {
     float m = 0.0f;
 #pragma unroll
     for (int c = 0; c < 2; ++c)
       m = fmaxf(m, fmaxf(fmaxf(fabsf(v[c].x), fabsf(v[c].y)), fmaxf(fabsf(v[c].z), fabsf(v[c].w))));
-    return wave_max(m);
+    return m;
   };
-  const float sq = quant_scale(amax8(yq), 127.0f);
-  qs[lane] = (int8_t)quant_one(q_own, sq);
+  float sq;
   int8_t kq = 0, vq = 0;
   float sk = 0.0f, sv = 0.0f;
   if constexpr (KV_NEW) {
-    sk = quant_scale(amax8(yk), 127.0f);
-    sv = quant_scale(amax8(yv), 127.0f);
-    kq = (int8_t)quant_one(k_own, sk);
-    vq = (int8_t)quant_one(v_own, sv);
+    // self: the q, k and v chains in one pass — three maxima through one DPP tree, the three
+    // scales behind one range test (absmax_scale127_n) and the three codes behind one near-tie
+    // vote (quant_one_n), so the chains interleave instead of running one after another
+    // between six rarely taken branches.  Where a vote fails all three take the true
+    // division, which equals the short form wherever that is exact: the same scales and codes
+    float am[3] = {lmax8(yq), lmax8(yk), lmax8(yv)};
+    wave_absmax_n<3>(am, 1e-5f);
+    absmax_scale127_n<3>(am);
+    const float own[3] = {q_own, k_own, v_own};
+    int code[3];
+    quant_one_n<3>(own, am, code);
+    sq = am[0]; sk = am[1]; sv = am[2];
+    qs[lane] = (int8_t)code[0];
+    kq = (int8_t)code[1];
+    vq = (int8_t)code[2];
+  } else {   // cross: q alone (the row absmax with quant_scale's 1e-5 floor in it)
+    sq = absmax_scale127(wave_absmax(lmax8(yq), 1e-5f));
+    qs[lane] = (int8_t)quant_one(q_own, sq);
+  }
+  if constexpr (KV_NEW) {
     const long row = kvb + step;
     a.kc[row * 512 + h * 64 + lane] = kq;     // cache append (attention.py: k/v of this step)
     a.vc[((vgb + (step >> 2)) * 512 + h * 64 + lane) * 4 + (step & 3)] = vq;
@@ -944,15 +982,6 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
 #pragma unroll
   for (int i = 0; i < NIT; ++i)
     sacc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(qf, __builtin_bit_cast(v4i, kr[i]), v4i{0, 0, 0, 0}, 0, 0, 0);
-  // the values of this head into LDS while the MFMAs run, then (self) the new value row
-  // over the stale one: one wave, whose LDS writes land in program order; the barrier after
-  // the PS writes orders both before the PV phase's reads
-#pragma unroll
-  for (int i = 0; i < NIT; ++i)
-    *reinterpret_cast<uint4*>(Vs + (min(4 * i + vg, glast) * 64 + vd) * 4) = vr[i];
-  if constexpr (KV_NEW) {
-    Vs[((step >> 2) * 64 + lane) * 4 + (step & 3)] = (uint8_t)vq;
-  }
   // key 16 i + fr is column fr of sacc[i] (C: column lane % 16, all rows equal): lane's key
   // lane is in sacc[fg], key lane + 64 in sacc[4 + fg]
   constexpr int NU = NIT > 4 ? 2 : 1;     // up to 64 rows: no second key slot
@@ -1012,21 +1041,36 @@ __global__ __launch_bounds__(64) void k_dec_attn(QTX_KA_PARAMS, DaTail kt) {
   // summed (c0 + c1) + (c2 + c3).  Per 16-key group the four chains' fmas are independent,
   // so the lone wave's dependent chain is a quarter of the keys (it was one fma per key,
   // 26-46 cycles each).  Padded keys: PS == 0 and a finite v, fma(0, v, acc) == acc.
-  // The values of 4 keys of the lane's dim in one dword (the 4-key group layout): one
-  // ds_read_b32 per chain step of 4 keys, each byte converted by one SDWA v_cvt_f32_i32.
+  // The values of 4 keys of the lane's dim in one dword (the 4-key group layout, vg4 as
+  // loaded in phase 0): each byte converted by one SDWA v_cvt_f32_i32.
   float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f;
-  const uint32_t* vl = reinterpret_cast<const uint32_t*>(Vs) + lane;
-  // every 16-key group's operands are read first (the NIT groups that cover the staged rows;
-  // those at or past nk16 are read and not used), so the chains pay the LDS latency once
+  if constexpr (KV_NEW) {
+    // (self) this step's value code over the stale byte: key `step` is byte step & 3 of the
+    // dword of group step >> 2, i.e. of vg4[step >> 4][(step >> 2) & 3].  With the position
+    // from the host nrows == step + 1, so that fragment is the last one; a step replayed at
+    // several positions (device counter) selects over all fragments
+    const int pq = (step >> 2) & 3, sh = 8 * (step & 3);
+    const uint32_t ins = (uint32_t)(uint8_t)vq << sh, keep = ~(0xffu << sh);
+    auto patch = [&](uint32_t (&f)[4], bool here) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) f[q] = here && q == pq ? (f[q] & keep) | ins : f[q];
+    };
+    if (a.host_step1 > 0) {
+      patch(vg4[NIT - 1], true);
+    } else {
+#pragma unroll
+      for (int g = 0; g < NIT; ++g) patch(vg4[g], g == (step >> 4));
+    }
+  }
+  // every 16-key group's PS operands are read first (the NIT groups that cover the staged
+  // rows; those at or past nk16 are read and not used), so the chains pay the LDS latency once
   // instead of once per group (a rolled loop waited on its reads every 16 keys)
   float4 pg[NIT][4];
-  uint32_t vg4[NIT][4];
 #pragma unroll
   for (int g = 0; g < NIT; ++g) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       pg[g][q] = *reinterpret_cast<const float4*>(PS + 16 * g + 4 * q);
-      vg4[g][q] = vl[(4 * g + q) * 64];
     }
     // in group order (LDS returns in issue order: the first chains then wait for group 0
     // alone, which the scheduler would otherwise issue last)
@@ -1146,7 +1190,7 @@ __global__ __launch_bounds__(256) void k_quant_h2048(const float* X, long ldx, i
 #pragma unroll
   for (int c = 0; c < 2; ++c)
     lm = fmaxf(lm, fmaxf(fmaxf(fabsf(t[c].x), fabsf(t[c].y)), fmaxf(fabsf(t[c].z), fabsf(t[c].w))));
-  lm = wave_max(lm);
+  lm = wave_absmax(lm);
   if (lane == 0) wm[wave] = lm;
   __syncthreads();
   const float sc = quant_scale(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3])), 127.0f);
@@ -1672,7 +1716,7 @@ __global__ __launch_bounds__(256) void k_skinny_wide_tok(QTX_KA_PARAMS, TkTail k
     uint32_t q[RPW][2];
     float sc[RPW];
     ln_rows512<RPW>(v, ga, gb);
-    quant_rows512<RPW>(v, q, sc);
+    quant_rows512<RPW, true>(v, q, sc);
 #pragma unroll
     for (int j = 0; j < RPW; ++j) {
       const int r = wave + 4 * j;
