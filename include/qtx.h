@@ -72,8 +72,12 @@ typedef struct qtx_model qtx_model;
  * Every config qtx_model_create accepts runs every model-level call (tests/
  * test_gpu_model_configs.py; the kernel chain per config: DESIGN.md, supported shapes):
  * the row-GEMM encoder / decoder chain needs d_ff % 512 == 0, the fused decode step
- * d_ff 512 or 2048 and tgt_vocab <= 8192; any other config takes the generic chain and the
- * unfused step, with the same results. */
+ * d_ff 512 or 2048, tgt_vocab <= 8192 and S, max_len <= 128; any other config or length takes
+ * the generic chain and the unfused step, with the same results.
+ * max_len: the rows of the positional table.  Every decoder-side entry takes up to 512 target
+ * positions and never more than the table holds (the same for S); 129 .. 512 positions run
+ * the unfused step and the generic attention kernel (supported shapes;
+ * tests/test_gpu_long_target.py). */
 typedef struct {
   int32_t src_vocab, tgt_vocab, n_layers, d_model, d_ff, n_heads, max_len, weight_bits;
 } qtx_config;
@@ -122,7 +126,10 @@ int32_t qtx_encoder_forward(const qtx_model* m, const float* x, const uint8_t* s
 
 /* Decoder graph: y [B,T,d] (= tgt_embed(ys), "global_in"), memory [B,S,d] ("global_in_1"),
  * src_mask [B,S] uint8 ("global_in_2"), tgt_mask uint8 [T,T] or [B,T,T]
- * (tgt_mask_batched = 0/1, "global_in_3") -> out [B,T,d] ("global_out"). */
+ * (tgt_mask_batched = 0/1, "global_in_3") -> out [B,T,d] ("global_out").
+ * T or S above 512 or above the positional table (cfg.max_len): QTX_E_INVALID, nothing
+ * written.  Past 128 target positions the self-attention runs the generic kernel
+ * (k_attention, up to 512 keys) under the [T,T] mask. */
 int32_t qtx_decoder_forward(const qtx_model* m, const float* y, const float* memory,
                             const uint8_t* src_mask, const uint8_t* tgt_mask,
                             int32_t tgt_mask_batched, int32_t B, int32_t T, int32_t S,
@@ -678,7 +685,10 @@ int32_t qtx_skinny_linear(int32_t amode, const int8_t* A, const float* sa, const
  *   (byte ((b*G4 + j/4)*512 + d)*4 + j%4 holds v[b][j][d]: one dword = 4 keys of one dim);
  *   skc/svc [B][kv_bs].  Out: fp32 context ctx [B,512]
  * and the per-head absmax pmax [8][B] (the next GEMM's per-token quantization, amode 2 of
- * qtx_skinny_linear with pmax_n = 8).  Keys <= 128.  The PV MatMul runs in the decoder's
+ * qtx_skinny_linear with pmax_n = 8).  Keys <= 128: this is the fused step's kernel; a decode
+ * with S or max_len above 128 runs the unfused step, whose attention takes up to 512 keys
+ * (qtx_attention_i8's kernel with the key count read from the step counter).  The PV MatMul
+ * runs in the decoder's
  * canonical order (four partial chains; qtx_attention_i8 with dec = 1).
  * y rows are ldy floats apart (ldy >= the row width, ldy % 4 == 0; y, kc and vc 16-byte
  * aligned, else QTX_E_INVALID).  Self: only cache row *step_dev (k, v and both scales) is

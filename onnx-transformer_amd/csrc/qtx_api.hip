@@ -1013,8 +1013,10 @@ int32_t qtx_decoder_forward_fault(const qtx_model* m, const float* y, const floa
                                   void* stream) {
   if (!m || !y || !memory || !src_mask || !tgt_mask || !out || !ws)
     return fail(QTX_E_INVALID, "null argument");
-  if (B <= 0 || T <= 0 || S <= 0 || T > 512 || S > 512)
-    return fail(QTX_E_INVALID, "bad shape B=%d T=%d S=%d", B, T, S);
+  // the rule of every decoder-side entry: at most 512 positions and no more than the
+  // positional table holds (y = tgt_embed(ys) exists for no longer target)
+  if (bad_decode_shape(m->cfg, B, S, T))
+    return fail(QTX_E_INVALID, "bad shape B=%d T=%d S=%d (table %d)", B, T, S, m->cfg.max_len);
   RC(check_workspace(ws_bytes, dec_ws(m->cfg, B, T, S)));
   RC(check_fault(m, f, 1, B, T, S));
   hipStream_t st = (hipStream_t)stream;

@@ -197,8 +197,8 @@ def test_reorder_op_wide_beam(torch, parents, t, grouped):
     reorder_case(torch, parents, t, grouped, POISONS[0])
 
 
-def reorder_case(torch, parents, t, grouped, poison):
-    K, B, L, ML, n = len(parents), 2, 2, MAX_LEN, t + 1
+def reorder_case(torch, parents, t, grouped, poison, ML=MAX_LEN):
+    K, B, L, n = len(parents), 2, 2, t + 1
     Rw = B * K
     krow = ML * 512
     vrow = ((ML + 3) // 4) * 2048 if grouped else ML * 512
