@@ -386,6 +386,61 @@ int32_t qtx_greedy_decode_kvfault(const qtx_model* m, const int64_t* src, const 
                                   const qtx_fault* fault, const qtx_cache_upset* upset,
                                   int32_t step, void* stream);
 
+/* ---- KV-cached fault decode: one independent trial per sentence ----
+ * A campaign runs thousands of the trials above (what a trial is:
+ * parallelized_inject_onnx_transformer.py:536-740), and sentences of a batch never interact:
+ * every op is per token or per (sentence, head), and the integer GEMM accumulators are exact.
+ * So one decode carries B trials, one per row, each at its own step; rows without a trial ride
+ * along as golden controls.  The contract is tests/kvtrials_ref.py: row b of this call equals,
+ * bit for bit, the stand-alone qtx_greedy_decode_kvfault call on sentence b alone — B = 1, scored
+ * form, the same S, source row and mask row, trial b's fault or upset at trial b's step — in
+ * ids, top_ids, top_logp and the record.
+ *
+ * trials: HOST array [B].  what 0: no trial (a golden row); 1: the step fault `fault`; 2: the
+ * cache upset `upset`; `step` as in the stand-alone call.  Coordinates are those of the B = 1
+ * call on the row's sentence:
+ *   Linear INPUT* / OUTPUT: row = 0.  Linear WEIGHT*: row = out channel.
+ *   Attention targets: the conventions above with b = 0, Sq = 1, Sk = step + 1 (self) or S
+ *   (cross); a WEIGHT16 window that does not contain row 0 has no effect.
+ *   Upset: row = j, the position within the sentence's cache (self: j < step; cross: j < S).
+ *   A WEIGHT fault is seen by its own row only: every row is its own machine.
+ * Two faults in one sentence (faults that interact) are not expressed here.
+ *
+ * Scored form only: the scored step and its tail always run, so ids follows the scored decode's
+ * rule; top_ids / top_logp may both be NULL (not copied out).  rec_ids / rec_logp [B, 2, 2],
+ * both or neither: row b holds the golden and the faulty top 2 of its own step, the golden pair
+ * from one golden cached run of that step made before anything is applied at it.  A row with
+ * what == 0 or step >= max_len - 1 decodes golden (its coordinates are not checked), and its
+ * record row is written as zeros.
+ * Schedule: the distinct trial steps in ascending order; between them the golden ranges run as
+ * in qtx_greedy_decode_dfault (same graphs, same path selection); at a step the upsets of that
+ * step flip, and if any row has a step fault there the step runs once, eager, on the whole
+ * batch through a GEMM that gives each row the fault of its own trial (and one recomputation
+ * of the affected (sentence, head) per attention-target trial); rows whose trial was earlier
+ * continue from their own diverged caches.
+ * Refused before anything is launched: trials NULL, a `what` outside 0..2, and per row what the
+ * stand-alone call refuses for B = 1 (the error text names the row): QTX_E_INVALID, or
+ * QTX_E_UNSUPPORTED for a step fault with 4-bit weights (upsets are allowed).  QTX_LIN_CK /
+ * QTX_LIN_CV step faults: QTX_E_UNSUPPORTED — the one-time [B * S] memory K/V projection is
+ * not made table-aware here (qtx_greedy_decode_kvfault takes them).  A short workspace:
+ * QTX_E_WORKSPACE.  B * tgt_vocab and B * max_len * d_model below 2^30.
+ * Writes exactly ids, top_ids, top_logp, rec_ids, rec_logp.  ws:
+ * qtx_greedy_kvtrials_workspace_size bytes; a dfault resume header on it is dropped.  The call
+ * waits for the stream once, before its first launch (the trial table's upload). */
+typedef struct {
+  int32_t what;            /* 0 none (golden row), 1 step fault, 2 cache upset */
+  int32_t step;
+  qtx_fault fault;         /* what == 1: module 1, B = 1 coordinates */
+  qtx_cache_upset upset;   /* what == 2: row = position within the sentence */
+} qtx_kv_trial;
+size_t qtx_greedy_kvtrials_workspace_size(const qtx_model* m, int32_t B, int32_t S,
+                                          int32_t max_len);
+int32_t qtx_greedy_decode_kvtrials(const qtx_model* m, const int64_t* src, const uint8_t* src_mask,
+                                   int32_t B, int32_t S, int32_t max_len, int64_t start,
+                                   int64_t* ids, int64_t* top_ids, float* top_logp,
+                                   int64_t* rec_ids, float* rec_logp, void* ws, size_t ws_bytes,
+                                   const qtx_kv_trial* trials, void* stream);
+
 /* ---- beam search with EOS stop ----
  * The reference has no beam search (its only decode is the fixed-length greedy loop above):
  * this entry cites generator.py:15 for the log-probabilities and nothing else.  The contract is
@@ -531,6 +586,17 @@ int32_t qtx_layernorm_quant(const float* x, const float* a, const float* b, int3
 int32_t qtx_linear_i8(const int8_t* A, const float* sa, const void* W, const float* sw,
                       const float* bias, int32_t M, int32_t N, int32_t K, int32_t weight_bits,
                       int32_t flags, const float* res, float* out, void* stream);
+
+/* qtx_linear_i8 with 8-bit weights where every row m carries a fault of its own (the GEMM of
+ * qtx_greedy_decode_kvtrials' eager step, k_gemm_rowfault): rows is a HOST array [M] of
+ * qtx_fault in B = 1 coordinates — kind NONE: none; INPUT* / OUTPUT: row = 0 (the row itself),
+ * the INPUT16 window over output columns; WEIGHT*: row = out channel, seen by row m alone, a
+ * WEIGHT16 window that does not contain row 0 without effect; module / layer / linear are not
+ * read.  Same expressions in the same order as qtx_linear_i8 with one fault.  A and W 16-byte
+ * aligned.  Synchronises the stream (the table lives for the length of the call). */
+int32_t qtx_linear_i8_rowfaults(const int8_t* A, const float* sa, const int8_t* W, const float* sw,
+                                const float* bias, int32_t M, int32_t N, int32_t K, int32_t flags,
+                                const float* res, float* out, const qtx_fault* rows, void* stream);
 
 /* Pack int8 values in [-8,7] [N,K] into int4 [N,K/2]. */
 int32_t qtx_pack_int4(const int8_t* q, int32_t N, int32_t K, uint8_t* packed, void* stream);

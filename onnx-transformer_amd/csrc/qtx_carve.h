@@ -354,6 +354,33 @@ inline size_t kvfault_ws(const qtx_config& c, const Groups& gr, int B, int S, in
   return align_up(ar.used);
 }
 
+// The trials decode's workspace (qtx_greedy_decode_kvtrials): the kvfault decode's (a prefix),
+// then the per-row fault table, the rows' trial steps, and the eager step's top 2.
+struct KvtrialsWS {
+  KvfaultWS k;
+  int* tab;             // [B][10] words: one RowFault (qtx_kernels.h) per row
+  int* tstep;           // [B] the row's trial step, -1: none
+  int64_t* pair_ids;    // [B, 2, 2]: [:, 1, :] the top 2 of the eager faulty step
+  float* pair_logp;
+};
+
+inline KvtrialsWS carve_kvtrials(Arena& ar, const qtx_config& c, const Groups& gr, int B, int S,
+                                 int max_len) {
+  KvtrialsWS w;
+  w.k = carve_kvfault(ar, c, gr, B, S, max_len);
+  w.tab = ar.take<int>((size_t)B * 10);
+  w.tstep = ar.take<int>((size_t)B);
+  w.pair_ids = ar.take<int64_t>((size_t)B * 4);
+  w.pair_logp = ar.take<float>((size_t)B * 4);
+  return w;
+}
+
+inline size_t kvtrials_ws(const qtx_config& c, const Groups& gr, int B, int S, int max_len) {
+  Arena ar;
+  carve_kvtrials(ar, c, gr, B, S, max_len);
+  return align_up(ar.used);
+}
+
 // Teacher-forced target scoring (qtx_score_targets).  One generator chunk's logits at the model-level call: at most 64 MiB, there only to bound
 // the workspace whatever R * T is.  Larger chunks measured faster all the way to one launch
 // (cfg2's shape, 2272 rows, V = 4444: generator + tail 1.043 / 0.371 / 0.235 / 0.204 ms with

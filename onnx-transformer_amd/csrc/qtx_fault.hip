@@ -262,8 +262,7 @@ int kvfault_check_fault(const qtx_model* m, const qtx_fault* f, int B, int S, in
 }
 
 // Where an upset lands: the code byte(s) or the scale word, as offsets checked against the
-// caches' extents here, on the host.
-struct UpsetAt { int8_t* c0; int8_t* c1; float* s; };
+// caches' extents here, on the host (UpsetAt: qtx_host.h).
 int kvfault_upset_at(const qtx_config& c, GreedyWS& g, const qtx_cache_upset* u, int B, int S,
                      int max_len, int step, bool fused, UpsetAt* at) {
   const long D = c.d_model;

@@ -1,5 +1,5 @@
 // qtx_host.h — what the C-ABI's host sources (qtx_model.hip, qtx_api.hip, qtx_fault.hip,
-// qtx_search.hip, qtx_ops.hip) share, internal to libqtx: the model handle, the
+// qtx_trials.hip, qtx_search.hip, qtx_ops.hip) share, internal to libqtx: the model handle, the
 // error and status helpers, the frame and the argument rules of a model-level entry, and the
 // stack and decode-step helpers that cross files.  Host code only: no kernel in any of them.
 #pragma once
@@ -261,5 +261,17 @@ StepRequest step_request(const qtx_model* m, std::vector<GreedyWS>& gv, const Gr
 // steps per graph of the decodes that run in chunks (QTX_GRAPH_STEPS, default 8)
 inline int graph_chunk() { return knobs().graph_steps > 0 ? knobs().graph_steps : 8; }
 int run_steps(const qtx_model* m, const StepRequest& rq, hipStream_t st);
+// a stack's attention arguments on the scratch s (kbs_rows: the K/V rows per sentence)
+AttnArgs attn_args(const Scratch& s, int B, int Sq, int Sk, long kbs_rows);
+
+// ---- the fault decodes' parts the trials decode is built from (qtx_fault.hip) -------------
+int dfault_steps(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, int t0, int t1,
+                 hipStream_t st);
+int record_top2(const float* logits, int B, int V, int64_t* rec_ids, float* rec_logp, int which,
+                hipStream_t st);
+int kvfault_check_fault(const qtx_model* m, const qtx_fault* f, int B, int S, int step);
+struct UpsetAt { int8_t* c0; int8_t* c1; float* s; };
+int kvfault_upset_at(const qtx_config& c, GreedyWS& g, const qtx_cache_upset* u, int B, int S,
+                     int max_len, int step, bool fused, UpsetAt* at);
 
 }  // namespace qtx

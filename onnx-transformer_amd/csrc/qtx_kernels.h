@@ -289,6 +289,28 @@ hipError_t launch_set_steps(int* step, int* gsteps, int G, int value, hipStream_
 // One stored cache bit flipped (k_cache_upset): bit 0..7 of the code bytes c0 / c1 (two copies
 // of one cell; either may be null), or bit 0..31 of the scale s — codes or a scale, not both.
 hipError_t launch_cache_upset(int8_t* c0, int8_t* c1, float* s, int bit, hipStream_t st);
+// The trials decode's kernels (csrc/qtx_rowfault.hip; include/qtx.h qtx_greedy_decode_kvtrials).
+// RowFault: the fault of ONE row of an M = B GEMM, in that GEMM's coordinates (FaultArgs's, the
+// row being the entry's own): the table holds one entry per row, and a launch for (step, layer,
+// gemm) applies to each output row the entry of that row alone, where it names this launch.
+//   FK_INPUT   A[row, col] bit-flipped: acc[row, n] += (flip(a) - a) * W[n, col], n in [lo, hi)
+//   FK_WEIGHT  W[wrow, col] bit-flipped as this row sees it: acc[row, wrow] += A[row, col] * (flip(w) - w)
+//   FK_OUTPUT  the MatMul output (before bias) at (row, col) replaced by value
+struct RowFault {
+  int step, layer, gemm, kind;   // kind FK_NONE: the row has no linear fault
+  int bit, col, wrow, lo, hi;
+  float value;
+};
+// k_gemm_rowfault: C = A . W^T with k_gemm's epilogue (GemmArgs; g.fault is not read) and the
+// table's corrections, expression for expression.  8-bit W; K % 64 == 0; A, W 16-byte aligned;
+// tab [g.M] (null: no faults).  The caller bounds every entry's col / wrow / lo / hi on the host.
+hipError_t launch_gemm_rowfault(const GemmArgs& g, const RowFault* tab, int step, int layer,
+                                int gemm, hipStream_t st);
+// k_trial_record: rec[b][which][:] = entry (b, step) of top_ids / top_logp [B][top_bs][2] for the
+// rows with tstep[b] == step; every other row of rec stays.
+hipError_t launch_trial_record(const int64_t* top_ids, const float* top_logp, long top_bs,
+                               int step, int B, const int* tstep, int which, int64_t* rec_ids,
+                               float* rec_logp, hipStream_t st);
 // Beam search (csrc/qtx_decode.hip; semantics: include/qtx.h, beam search).  Rows r = b * K + k.
 //   select:  the tail of a beam step on logits [B*K][V]: per sentence the K best of the K * V
 //            candidates; rewrites score / fin / len [B*K] in place, writes parent [B*K], the

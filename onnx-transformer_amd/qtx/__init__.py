@@ -9,6 +9,8 @@ Public surface mirrors the reference's entry points:
   decode_fault_sweep(model, src, src_mask, max_len, start_symbol, trials)   ~ a campaign's trials
   greedy_decode_kvfault(model, src, src_mask, max_len, fault= | upset=, step=)   a fault of the
                                                KV-cached decode itself (no reference counterpart)
+  greedy_decode_kvfault_trials(model, src, src_mask, max_len, start_symbol, trials)   one such
+                                               trial per sentence in one decode; kvfault_campaign
   score_targets(model, src, src_mask, tgt) -> TargetScores   ~ EncoderDecoder.forward on a given
                                                                target + log_softmax
 """
@@ -18,7 +20,8 @@ from .weights import (BOS, DEFAULT_SEED, EOS, PAD, UNK, ModelConfig, load_checkp
 __all__ = ["BOS", "EOS", "PAD", "UNK", "DEFAULT_SEED", "ModelConfig", "load_checkpoint",
            "positional_table", "synthetic_state_dict", "tensor_order", "QtxModel",
            "InferenceSession", "run_module", "set_default_model", "greedy_decode",
-           "greedy_decode_fault", "greedy_decode_kvfault", "decode_fault_sweep", "plan_sweep",
+           "greedy_decode_fault", "greedy_decode_kvfault", "greedy_decode_kvfault_trials",
+           "kvfault_campaign", "decode_fault_sweep", "plan_sweep",
            "SweepStats", "Scores", "FaultStepRecord", "make_src_mask", "score_targets",
            "rescore_beam", "TargetScores", "lib"]
 
@@ -32,6 +35,7 @@ def __getattr__(name):
         from . import session
         return getattr(session, name)
     if name in ("greedy_decode", "greedy_decode_fault", "greedy_decode_kvfault",
+                "greedy_decode_kvfault_trials", "kvfault_campaign",
                 "decode_fault_sweep", "plan_sweep", "SweepStats", "Scores", "FaultStepRecord",
                 "make_src_mask", "score_targets", "rescore_beam", "TargetScores"):
         from . import decode

@@ -62,8 +62,14 @@ class CacheUpset(C.Structure):
                 ("col", I32), ("reserved", I32)]
 
 
+class KvTrial(C.Structure):
+    """struct qtx_kv_trial (include/qtx.h)."""
+    _fields_ = [("what", I32), ("step", I32), ("fault", Fault), ("upset", CacheUpset)]
+
+
 FP = C.POINTER(Fault)
 UP = C.POINTER(CacheUpset)
+TP = C.POINTER(KvTrial)
 
 # name -> (restype, argtypes); must match include/qtx.h
 SIGNATURES = {
@@ -113,6 +119,9 @@ SIGNATURES = {
     "qtx_greedy_kvfault_workspace_size": (SZ, [P, I32, I32, I32]),
     "qtx_greedy_decode_kvfault": (I32, [P, P, P, I32, I32, I32, I64, P, P, P, P, P, P, SZ, FP,
                                         UP, I32, P]),
+    "qtx_greedy_kvtrials_workspace_size": (SZ, [P, I32, I32, I32]),
+    "qtx_greedy_decode_kvtrials": (I32, [P, P, P, I32, I32, I32, I64, P, P, P, P, P, P, SZ, TP, P]),
+    "qtx_linear_i8_rowfaults": (I32, [P, P, P, P, P, I32, I32, I32, I32, P, P, FP, P]),
     "qtx_beam_workspace_size": (SZ, [P, I32, I32, I32, I32]),
     "qtx_beam_decode": (I32, [P, P, P, I32, I32, I32, I32, I64, I64, I64, I32, P, P, P,
                               C.POINTER(I32), P, SZ, P]),

@@ -348,6 +348,58 @@ def greedy_decode_kvfault(model: QtxModel, src, src_mask, max_len: int, start_sy
     return ys.cpu().numpy(), Scores(top_ids.cpu().numpy(), top_logp.cpu().numpy(), record)
 
 
+def greedy_decode_kvfault_trials(model: QtxModel, src, src_mask, max_len: int,
+                                 start_symbol: int = 0, trials=()):
+    """One KV-cached scored decode that carries one independent kvfault trial per sentence
+    (qtx_greedy_decode_kvtrials; the contract is tests/kvtrials_ref.py): ``trials`` is a list of
+    B items, each None (a golden row) or (Fault | CacheUpset, step) in the coordinates of
+    greedy_decode_kvfault on that sentence ALONE (linear INPUT / OUTPUT row 0, attention b = 0,
+    an upset's row the position within the sentence's cache).  Row b equals that stand-alone
+    call bit for bit.  Memory K/V projection faults (CK / CV) are not taken here.
+    Returns (ys int64 [B, max_len], Scores, records): records[b] a FaultStepRecord with arrays
+    [2] (the golden and the faulty top 2 of row b's own step), or None for a row without an
+    applied trial."""
+    import torch
+    src = np.ascontiguousarray(np.asarray(src), np.int64)
+    B, S = src.shape
+    trials = list(trials)
+    srcd = torch.from_numpy(src).to(model.device)
+    md = to_u8_mask(src_mask, model.device).reshape(B, S)
+    ys, top_ids, top_logp, rec_ids, rec_logp = model.greedy_kvtrials(
+        srcd, md, trials, max_len=max_len, start=start_symbol)
+    model.check()
+    ri, rl = rec_ids.cpu().numpy(), rec_logp.cpu().numpy()
+    records = [None if tr is None or not 0 <= int(tr[1]) < max_len - 1 else
+               FaultStepRecord(int(tr[1]), ri[b, 0].copy(), rl[b, 0].copy(), ri[b, 1].copy(),
+                               rl[b, 1].copy())
+               for b, tr in enumerate(trials)]
+    return ys.cpu().numpy(), Scores(top_ids.cpu().numpy(), top_logp.cpu().numpy()), records
+
+
+def kvfault_campaign(model: QtxModel, src_row, mask_row, max_len: int, trials, batch: int = 32,
+                     start_symbol: int = 0):
+    """A campaign of kvfault trials on ONE sentence: src_row [S] (or [1, S]) and its mask row are
+    replicated over ``batch`` rows, ``trials`` (any number of (Fault | CacheUpset, step) or None)
+    are cut into batches of ``batch`` — the last padded with None — and each batch is one
+    greedy_decode_kvfault_trials call.  Returns one (ys [max_len], Scores with arrays
+    [max_len-1, 2], record) per trial, in the caller's order."""
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    trials = list(trials)
+    src = np.repeat(np.asarray(src_row, np.int64).reshape(1, -1), batch, axis=0)
+    S = src.shape[1]
+    mask = np.repeat((np.asarray(mask_row) != 0).reshape(1, 1, S), batch, axis=0)
+    out = []
+    for k in range(0, len(trials), batch):
+        chunk = trials[k:k + batch]
+        ys, sc, recs = greedy_decode_kvfault_trials(
+            model, src, mask, max_len, start_symbol, chunk + [None] * (batch - len(chunk)))
+        out += [(ys[b].copy(), Scores(sc.top_ids[b].copy(), sc.top_logp[b].copy()), recs[b])
+                for b in range(len(chunk))]
+    return out
+
+
 @dataclasses.dataclass
 class SweepStats:
     """decode_fault_sweep's counts: trials in all; ``n_resumed`` whose fault changed a token,

@@ -307,6 +307,36 @@ class QtxModel:
         return (ids, top_ids, top_logp, rec_ids, rec_logp) if scores else ids
 
     @_on_device
+    def greedy_kvtrials(self, src, src_mask_u8, trials, max_len: int = 72, start: int = 0):
+        """One KV-cached scored decode with one independent trial per sentence
+        (qtx_greedy_decode_kvtrials).  trials: B items, each None or (qtx.fault.Fault |
+        qtx.fault.CacheUpset, step) in the coordinates of the B = 1 call on that sentence.
+        Returns (ids, top_ids, top_logp, rec_ids, rec_logp) on the device; the record row of a
+        sentence whose trial is None or never applied is zeros."""
+        from .fault import CacheUpset, Fault
+        B, S = src.shape
+        if len(trials) != B:
+            raise ValueError(f"{len(trials)} trials for {B} sentences")
+        arr = (_lib.KvTrial * B)()
+        for b, tr in enumerate(trials):
+            if tr is None:
+                continue
+            what, step = tr
+            arr[b].step = int(step)
+            if isinstance(what, Fault):
+                arr[b].what, arr[b].fault = 1, what.to_c()
+            elif isinstance(what, CacheUpset):
+                arr[b].what, arr[b].upset = 2, what.to_c()
+            else:
+                raise TypeError(f"trial {b}: a Fault or a CacheUpset, not {type(what).__name__}")
+        ids, top_ids, top_logp, rec_ids, rec_logp = self._dfault_outputs(B, max_len, True)
+        ws = self.workspace(_lib.lib().qtx_greedy_kvtrials_workspace_size(self.handle, B, S, max_len))
+        _lib.call("qtx_greedy_decode_kvtrials", self.handle, _ptr(src), _ptr(src_mask_u8), B, S,
+                  max_len, int(start), _ptr(ids), _ptr(top_ids), _ptr(top_logp), _ptr(rec_ids),
+                  _ptr(rec_logp), _ptr(ws), ws.numel(), arr, _stream(self.device))
+        return ids, top_ids, top_logp, rec_ids, rec_logp
+
+    @_on_device
     def embed(self, ids, which: str = "src", pos0: int = 0):
         torch = _torch()
         B, T = ids.shape

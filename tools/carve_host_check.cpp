@@ -284,6 +284,27 @@ static void decode_case(const qtx_config& c, const Groups& gr, int B, int S, int
     r.add("rec_logp", w.rec_logp, (size_t)B * 4);
     r.verify(b.ar.base, z.kvfault);
   }
+  {   // the trials decode: KvfaultWS a prefix, then the table, the steps and the eager pair
+    const size_t bytes = kvtrials_ws(c, gr, B, S, max_len);
+    CHECK(bytes >= z.kvfault);
+    Block b(bytes);
+    const KvtrialsWS w = carve_kvtrials(b.ar, c, gr, B, S, max_len);
+    b.spent();
+    Arena again;
+    again.base = b.ar.base; again.cap = z.kvfault;
+    const KvfaultWS k = carve_kvfault(again, c, gr, B, S, max_len);
+    same_greedy(k.g, w.k.g);
+    CHECK(k.rec_ids == w.k.rec_ids && k.rec_logp == w.k.rec_logp && w.k.g.no_fold);
+    Regions r;
+    add_greedy(r, w.k.g, c, gr, B, S, max_len, true);
+    r.add("rec_ids", w.k.rec_ids, (size_t)B * 4);
+    r.add("rec_logp", w.k.rec_logp, (size_t)B * 4);
+    r.add("tab", w.tab, (size_t)B * 10);
+    r.add("tstep", w.tstep, (size_t)B);
+    r.add("pair_ids", w.pair_ids, (size_t)B * 4);
+    r.add("pair_logp", w.pair_logp, (size_t)B * 4);
+    r.verify(b.ar.base, bytes);
+  }
 }
 
 static void score_case(const qtx_config& c, int B, int S, int T, int K, int nf) {
