@@ -40,6 +40,11 @@
  * 16-byte aligned (any hipMalloc'd base does).  The entry points that take a stride
  * (qtx_linear_rows: ldo8 / o8_ts; qtx_skinny_linear: ldx; qtx_decode_attention: ldy) check
  * the base and the stride on the host and return QTX_E_INVALID before anything is launched.
+ * 16 bytes is all any entry point needs, and any 16-byte aligned base is accepted: a view
+ * into a larger allocation, a sub-allocated arena, a workspace at 16 (mod 256) (its carved
+ * sub-buffers then sit at 16 (mod 256) too).  tests/test_gpu_bounds.py (ids align16) and
+ * tests/test_gpu_min_align.py run every entry point that takes a device pointer with every
+ * pointer at 16 (mod 256) against the oracle.
  * Extents are exact: a call writes nothing outside the output and scratch extents stated
  * here, and writes every element of them (tests/test_gpu_bounds.py).
  */

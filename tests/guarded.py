@@ -20,6 +20,11 @@ a value that changes the result if a kernel uses it (NaN for fp32 rows and parti
 0x7f for int8 codes, the complement of the neighbouring value for masks); it asserts only
 through results.
 
+Every payload and input is 256-byte aligned by default; skew=16 (any multiple of 16 below
+256) puts it at that residue instead — 16 (mod 256) is the least alignment include/qtx.h
+accepts, the case of a caller that sub-allocates one arena or passes a view.  skewed() does
+the same for a plain exact-size input.
+
 Works on CPU tensors too (tests/test_guarded_helper.py), device="cpu".
 """
 import numpy as np
@@ -58,11 +63,17 @@ class _Check:
                     f"payload (poison 0x{self.poison:02X}, found 0x{got:02X})")
 
 
-def _alloc(torch, payload_bytes, guard_bytes, poison, device):
-    total = 2 * guard_bytes + payload_bytes + ALIGN
+def _check_skew(skew):
+    assert 0 <= skew < ALIGN and skew % 16 == 0, f"skew {skew}: a multiple of 16 below {ALIGN}"
+    return int(skew)
+
+
+def _alloc(torch, payload_bytes, guard_bytes, poison, device, skew=0):
+    skew = _check_skew(skew)
+    total = 2 * guard_bytes + payload_bytes + ALIGN + skew
     buf = torch.full((total,), poison, dtype=torch.uint8, device=device)
-    off = guard_bytes + (-(buf.data_ptr() + guard_bytes)) % ALIGN
-    assert (buf.data_ptr() + off) % ALIGN == 0 and off + payload_bytes + guard_bytes <= total
+    off = guard_bytes + (-(buf.data_ptr() + guard_bytes)) % ALIGN + skew
+    assert (buf.data_ptr() + off) % ALIGN == skew and off + payload_bytes + guard_bytes <= total
     return buf, off, total
 
 
@@ -71,26 +82,29 @@ def guard_bytes_for(pitch_bytes):
     return _round_up(max(GUARD_MIN, 2 * int(pitch_bytes)), ALIGN)
 
 
-def guarded(torch, shape, dtype, poison, device="cuda", name="buffer", pitch_bytes=None):
+def guarded(torch, shape, dtype, poison, device="cuda", name="buffer", pitch_bytes=None,
+            skew=0):
     """A contiguous payload of `shape` / `dtype` between two poisoned guards.
 
-    Returns (payload, check): payload is a view of the buffer (256-byte aligned, poisoned),
-    check() asserts that both guards still hold the poison.  pitch_bytes: the row size the
-    guards are sized for (default: the payload's last dimension)."""
+    Returns (payload, check): payload is a view of the buffer (poisoned; its address is
+    `skew` mod 256, skew a multiple of 16: 0 by default, 16 = the least alignment
+    include/qtx.h accepts), check() asserts that both guards still hold the poison.
+    pitch_bytes: the row size the guards are sized for (default: the payload's last
+    dimension)."""
     shape = tuple(int(s) for s in (shape if hasattr(shape, "__len__") else (shape,)))
     item = torch.empty((), dtype=dtype).element_size()
     n = int(np.prod(shape)) if shape else 1
     nbytes = n * item
     row = pitch_bytes if pitch_bytes is not None else (shape[-1] if shape else 1) * item
     gb = guard_bytes_for(row)
-    buf, off, total = _alloc(torch, nbytes, gb, poison, device)
+    buf, off, total = _alloc(torch, nbytes, gb, poison, device, skew)
     payload = buf[off:off + nbytes].view(dtype).view(shape)
     segs = [(-off, 0, "front guard"), (nbytes, total - off, "back guard")]
     return payload, _Check(buf, off, segs, poison, name)
 
 
 def guarded_pitched(torch, rows, row_bytes, pitch_bytes, dtype, poison, device="cuda",
-                    name="buffer"):
+                    name="buffer", skew=0):
     """`rows` rows of `row_bytes` bytes, `pitch_bytes` apart; the gap bytes between the rows
     are guard too (the payload ends with the last row's last byte).
 
@@ -99,7 +113,7 @@ def guarded_pitched(torch, rows, row_bytes, pitch_bytes, dtype, poison, device="
     assert row_bytes <= pitch_bytes and row_bytes % item == 0 and pitch_bytes % item == 0
     nbytes = (rows - 1) * pitch_bytes + row_bytes
     gb = guard_bytes_for(pitch_bytes)
-    buf, off, total = _alloc(torch, nbytes, gb, poison, device)
+    buf, off, total = _alloc(torch, nbytes, gb, poison, device, skew)
     flat = buf[off:off + _round_up(nbytes, item)].view(dtype)
     payload = torch.as_strided(flat, (rows, row_bytes // item), (pitch_bytes // item, 1))
     segs = [(-off, 0, "front guard")]
@@ -126,7 +140,24 @@ class _PitchedCheck(_Check):
         _Check(self.buf, self.off, plain, self.poison, self.name)()
 
 
-def padded_input(torch, array, pitch, fill, device="cuda"):
+def skewed(torch, array, skew=0, device="cuda"):
+    """A plain exact-size input: the device copy of the numpy `array` at an address that is
+    `skew` mod 256 (a view into a slightly larger allocation, which it keeps alive)."""
+    a = np.ascontiguousarray(array)
+    skew = _check_skew(skew)
+    src = torch.from_numpy(a)
+    if skew == 0 and device != "cpu":
+        return src.to(device)                   # a fresh allocation: at least 256-byte aligned
+    nbytes = a.size * a.itemsize
+    buf = torch.zeros((nbytes + 2 * ALIGN,), dtype=torch.uint8, device=device)
+    off = (-buf.data_ptr()) % ALIGN + skew
+    t = buf[off:off + nbytes].view(src.dtype).view(a.shape)
+    assert t.data_ptr() % ALIGN == skew
+    t.copy_(src)
+    return t
+
+
+def padded_input(torch, array, pitch, fill, device="cuda", skew=0):
     """The rows of `array` embedded at wider strides, gaps and a tail filled with `fill`.
 
     array: numpy [..., W].  pitch: the row stride in elements (2-D arrays), or a tuple of
@@ -134,7 +165,8 @@ def padded_input(torch, array, pitch, fill, device="cuda"):
     fill: a value of the array's dtype (NaN, 0x7f, ...) or "complement": each gap element
     holds the complement (0 <-> 1) of the nearest payload element before it.
     Returns the flat device tensor; element [i, j, ..., w] sits at i*stride0 + j*stride1 + w.
-    The tail after the last row is one more outermost stride (at least 64 elements)."""
+    The tail after the last row is one more outermost stride (at least 64 elements).
+    skew: the tensor's address mod 256, as in skewed()."""
     a = np.ascontiguousarray(array)
     strides = (pitch,) if np.isscalar(pitch) else tuple(pitch)
     assert len(strides) == a.ndim - 1 and strides[-1] >= a.shape[-1]
@@ -156,4 +188,4 @@ def padded_input(torch, array, pitch, fill, device="cuda"):
     else:
         flat = np.full(n, fill, a.dtype)
         flat[idx] = rows
-    return torch.from_numpy(flat).to(device)
+    return skewed(torch, flat, skew, device)

@@ -11,6 +11,13 @@ complementary mask value, which change the result if a kernel uses them.
 
 Shapes are the smallest at which each code path can still go wrong: ragged in every
 blocked dimension, one M per row-block size a launcher can choose.
+
+Every case runs at two alignments (the `gb` fixture): align256 (the ids that name only a
+poison), where each pointer is a fresh allocation or a 256-byte aligned payload, and
+align16 (ids align16-poisonA5; one poison only), where every
+pointer of the case — inputs, scales, biases, masks, weights, packed weights, outputs and
+workspaces — sits at 16 (mod 256), the least alignment include/qtx.h promises to accept.  A
+workspace at such a base puts every carved sub-buffer at 16 (mod 256) too.
 """
 import ctypes as C
 import os
@@ -22,7 +29,7 @@ import pytest
 from oracle import qtx_oracle as O
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from guarded import POISONS, guarded, guarded_pitched, padded_input  # noqa: E402
+from guarded import POISONS, guarded, guarded_pitched, padded_input, skewed  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -39,17 +46,12 @@ def torch():
     return torch
 
 
-@pytest.fixture(params=POISONS, ids=lambda p: f"poison{p:02X}")
-def poison(request):
-    return request.param
-
-
 class Guards:
     """The guarded buffers of one case: new() / pitched() / init() allocate, check()
     synchronises and asserts every guard."""
 
-    def __init__(self, torch, poison):
-        self.torch, self.poison, self.checks, self.keep = torch, poison, [], []
+    def __init__(self, torch, poison, skew=0):
+        self.torch, self.poison, self.skew, self.checks, self.keep = torch, poison, skew, [], []
 
     def _tdtype(self, dt):
         t = self.torch
@@ -59,13 +61,13 @@ class Guards:
 
     def new(self, shape, dtype, name, pitch_bytes=None):
         t, c = guarded(self.torch, shape, self._tdtype(dtype), self.poison, name=name,
-                       pitch_bytes=pitch_bytes)
+                       pitch_bytes=pitch_bytes, skew=self.skew)
         self.checks.append(c)
         return t
 
     def pitched(self, rows, row_bytes, pitch_bytes, dtype, name):
         t, c = guarded_pitched(self.torch, rows, row_bytes, pitch_bytes, self._tdtype(dtype),
-                               self.poison, name=name)
+                               self.poison, name=name, skew=self.skew)
         self.checks.append(c)
         return t
 
@@ -78,12 +80,12 @@ class Guards:
 
     def dev(self, a):
         """A plain (exact-size) input."""
-        t = self.torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        t = skewed(self.torch, a, self.skew)
         self.keep.append(t)
         return t
 
     def pad(self, a, pitch, fill):
-        t = padded_input(self.torch, a, pitch, fill)
+        t = padded_input(self.torch, a, pitch, fill, skew=self.skew)
         self.keep.append(t)
         return t
 
@@ -102,9 +104,16 @@ class Guards:
         assert bad.size == 0, f"{name}: payload byte {bad[0]} written"
 
 
-@pytest.fixture
-def gb(torch, poison):
-    return Guards(torch, poison)
+# (poison, skew): align256 under both poisons — these keep the ids they had before the
+# alignment parameter existed — and align16 under 0xA5 only: the unwritten-element argument of
+# the two poisons is made at align256, and the file's time grows by half instead of doubling
+GB_PARAMS = [(p, 0) for p in POISONS] + [(POISONS[0], 16)]
+
+
+@pytest.fixture(params=GB_PARAMS,
+                ids=[f"poison{p:02X}" if not k else f"align{k}-poison{p:02X}" for p, k in GB_PARAMS])
+def gb(request, torch):
+    return Guards(torch, *request.param)
 
 
 def P(t):
@@ -432,8 +441,9 @@ def test_linear_rows_misaligned_is_invalid(gb, kp):
     os_ = gb.new((3, M), f32, "os")
     ok = dict(epi=0, out8=out8, ldo8=512, o8_ts=M * 512, os=os_, os_ts=M)
     for bad in (dict(ldo8=520 - 4), dict(o8_ts=M * 512 + 8), dict(out8=out8.data_ptr() + 4),
-                dict(ldo8=496)):
-        assert rows_rc(**{**ok, **bad, **base}) == E_INVALID, bad
+                dict(out8=out8.data_ptr() + 8), dict(A=base["A"].data_ptr() + 8),
+                dict(W=base["W"].data_ptr() + 8), dict(ldo8=496)):
+        assert rows_rc(**{**ok, **base, **bad}) == E_INVALID, bad
     gb.check()
     gb.assert_poison(out8, "out8")
     gb.assert_poison(os_, "os")
@@ -815,7 +825,8 @@ def test_skinny_rejected_shapes(gb, oracle_model):
     X = gb.pad(r["x"], 512 + LDX_PAD, NAN)
     for amode in (1, 2, 3):
         rr = dict(r, parts=np.abs(r["x"]).max(-1)[None, :].astype(f32), n=1)
-        for kw in (dict(ldx=512 + 10), dict(ldx=508), dict(X=C.c_void_p(X.data_ptr() + 4))):
+        for kw in (dict(ldx=512 + 10), dict(ldx=508), dict(X=C.c_void_p(X.data_ptr() + 4)),
+                   dict(X=C.c_void_p(X.data_ptr() + 8))):
             rc, out, pm = _skinny_run(gb, rr, amode, M, 512, 512, 8, 0, **{"X": X, **kw})
             assert rc == E_INVALID, (amode, kw)
             gb.assert_poison(out, "out")
@@ -928,7 +939,8 @@ def test_decode_attention_misaligned_is_invalid(gb):
     sk, sv = gb.init(np.ones((B, kv_bs), f32), "skc"), gb.init(np.ones((B, kv_bs), f32), "svc")
     ctx, pm = gb.new((B, 512), f32, "ctx"), gb.new((8, B), f32, "pmax")
     step = gb.dev(np.array([0], np.int32))
-    for yp, ldy in ((y.data_ptr(), 1538), (y.data_ptr(), 1024), (y.data_ptr() + 4, 1536)):
+    for yp, ldy in ((y.data_ptr(), 1538), (y.data_ptr(), 1024), (y.data_ptr() + 4, 1536),
+                    (y.data_ptr() + 8, 1536)):
         rc = lib().qtx_decode_attention(1, C.c_void_p(yp), ldy, P(kc), P(vc), P(sk), P(sv), kv_bs,
                                         P(step), 0, S0, B, P(ctx), P(pm), S0)
         assert rc == E_INVALID, (yp - y.data_ptr(), ldy)

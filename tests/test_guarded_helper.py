@@ -12,7 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from guarded import (GUARD_MIN, POISONS, guard_bytes_for, guarded, guarded_pitched,  # noqa: E402
-                     padded_input)
+                     padded_input, skewed)
 
 
 @pytest.mark.parametrize("poison", POISONS)
@@ -157,3 +157,79 @@ def test_padded_input_mask_complement():
             nxt = (b * m_bs + (i + 1) * m_is) if i + 1 < Sq else (b + 1) * m_bs
             assert (t[o + Sk:nxt] == (m[b, i, -1] == 0)).all()
     assert t.size >= B * m_bs
+
+
+# ---- skew: payloads at the least alignment include/qtx.h accepts (16 mod 256) -------------
+@pytest.mark.parametrize("skew", [0, 16, 48, 240])
+def test_skew_sets_the_address_residue(skew):
+    t, check = guarded(torch, (5, 512), torch.float32, 0xA5, device="cpu", skew=skew)
+    assert t.data_ptr() % 256 == skew and t.data_ptr() == check.buf.data_ptr() + check.off
+    assert t.shape == (5, 512) and t.is_contiguous() and (t.view(torch.uint8) == 0xA5).all()
+    # the guards keep their minimum sizes
+    assert check.off >= GUARD_MIN and check.buf.numel() - check.off - 5 * 2048 >= GUARD_MIN
+    check()
+    p, pc = guarded_pitched(torch, 7, 1536, 1600, torch.int8, 0xA5, device="cpu", skew=skew)
+    assert p.data_ptr() % 256 == skew and p.stride() == (1600, 1)
+    assert pc.off >= GUARD_MIN and pc.buf.numel() - pc.off - (6 * 1600 + 1536) >= GUARD_MIN
+    pc()
+    x = np.arange(35, dtype=np.float32).reshape(5, 7)
+    s = skewed(torch, x, skew, device="cpu")
+    assert s.data_ptr() % 256 == skew and s.is_contiguous()
+    np.testing.assert_array_equal(s.numpy(), x)
+    ids = skewed(torch, np.arange(6, dtype=np.int64).reshape(2, 3), skew, device="cpu")
+    assert ids.data_ptr() % 256 == skew and ids.dtype == torch.int64
+    q = padded_input(torch, np.full((2, 8), -3, np.int8), 24, 0x7f, device="cpu", skew=skew)
+    assert q.data_ptr() % 256 == skew
+    assert (q.numpy()[8:24] == 127).all() and (q.numpy()[24:32] == -3).all()
+
+
+@pytest.mark.parametrize("skew", [4, 8, 24, 256, -16])
+def test_skew_must_be_a_multiple_of_16_below_256(skew):
+    with pytest.raises(AssertionError):
+        guarded(torch, (4,), torch.float32, 0xA5, device="cpu", skew=skew)
+    with pytest.raises(AssertionError):
+        skewed(torch, np.zeros(4, np.float32), skew, device="cpu")
+
+
+@pytest.mark.parametrize("poison", POISONS)
+@pytest.mark.parametrize("where,offset", [("front", -1), ("front", -16), ("front", -4096),
+                                          ("back", 0), ("back", 15), ("back", 3 * 2048 + 17)])
+def test_skewed_guard_byte_fails_with_offset(poison, where, offset):
+    """The byte just before and just after a payload at 16 (mod 256) is guard, and a change
+    is reported relative to the payload, not to the 256-byte boundary below it."""
+    t, check = guarded(torch, (7, 512), torch.int8, poison, device="cpu", name="out8", skew=16)
+    nbytes = 7 * 512
+    rel = offset if where == "front" else nbytes + offset
+    raw = check.buf.numpy()
+    addr = t.data_ptr() + rel - check.buf.data_ptr()        # located through the payload's address
+    raw[addr] = poison ^ 0xFF
+    with pytest.raises(AssertionError) as e:
+        check()
+    msg = str(e.value)
+    assert f"{where} guard" in msg and f"byte offset {rel} " in msg and "out8" in msg
+    raw[addr] = poison
+    t.fill_(1)                                               # the payload itself is not guard
+    check()
+
+
+def test_skewed_pitched_gaps_are_checked():
+    M = 7
+    t, check = guarded_pitched(torch, M, 1536, 1600, torch.int8, 0x5A, device="cpu", skew=16)
+    t.fill_(3)
+    check()
+    raw = check.buf.numpy()
+    base = t.data_ptr() - check.buf.data_ptr()
+    assert (raw[base:base + 6 * 1600 + 1536].view(np.int8) == 3).sum() == M * 1536
+    at = 2 * 1600 + 1536                   # the first gap byte after row 2
+    raw[base + at] = 0
+    with pytest.raises(AssertionError) as e:
+        check()
+    assert "pitch gap after row 2" in str(e.value) and f"byte offset {at} " in str(e.value)
+    raw[base + at] = 0x5A
+    raw[base - 1] = 0                      # the byte before row 0
+    with pytest.raises(AssertionError, match="front guard changed at byte offset -1 "):
+        check()
+    raw[base - 1] = 0x5A
+    raw[base + 6 * 1600 + 1536] = 0        # the byte after the last row
+    with pytest.raises(AssertionError, match="back guard changed at byte offset 11136 "):
+        check()
