@@ -903,11 +903,11 @@ StepRequest step_request(const qtx_model* m, std::vector<GreedyWS>& gv, const Gr
   return rq;
 }
 
-int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S, int max_len,
-               int64_t start, const qtx_fault* f, hipStream_t st) {
+// The steps of a greedy decode after its prologue, with the decode's path selection (the plain
+// or, with g.top_ids, the scored step).
+int greedy_steps(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, hipStream_t st) {
   const qtx_config& c = m->cfg;
   const bool fused = greedy_fused(c, S, max_len);
-  RC(greedy_prologue(m, g, src, B, S, max_len, start, f, fused, st));
   if (!fused) {
     for (int t = 0; t + 1 < max_len; ++t) RC(greedy_step_unfused(m, g, B, S, max_len, g.ids, g.mask, st));
     return QTX_OK;
@@ -934,6 +934,12 @@ int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S
   rq.plan = {{per_graph, (max_len - 1) / per_graph, 0}};
   rq.timed = knobs().time_graph;
   return run_steps(m, rq, st);
+}
+
+int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S, int max_len,
+               int64_t start, const qtx_fault* f, hipStream_t st) {
+  RC(greedy_prologue(m, g, src, B, S, max_len, start, f, greedy_fused(m->cfg, S, max_len), st));
+  return greedy_steps(m, g, B, S, max_len, st);
 }
 
 }  // namespace qtx

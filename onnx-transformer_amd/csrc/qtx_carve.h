@@ -381,6 +381,27 @@ inline size_t kvtrials_ws(const qtx_config& c, const Groups& gr, int B, int S, i
   return align_up(ar.used);
 }
 
+// The encoder trials decode's workspace (qtx_greedy_decode_enctrials): the scored greedy
+// decode's (a prefix), then the per-token-row fault table.
+struct EnctrialsWS {
+  GreedyWS g;
+  int* tab;             // [B * S][10] words: one RowFault (qtx_kernels.h) per token row
+};
+
+inline EnctrialsWS carve_enctrials(Arena& ar, const qtx_config& c, const Groups& gr, int B, int S,
+                                   int max_len) {
+  EnctrialsWS w;
+  w.g = carve_greedy(ar, c, gr, B, S, max_len, true);
+  w.tab = ar.take<int>((size_t)B * S * 10);
+  return w;
+}
+
+inline size_t enctrials_ws(const qtx_config& c, const Groups& gr, int B, int S, int max_len) {
+  Arena ar;
+  carve_enctrials(ar, c, gr, B, S, max_len);
+  return align_up(ar.used);
+}
+
 // Teacher-forced target scoring (qtx_score_targets).  One generator chunk's logits at the model-level call: at most 64 MiB, there only to bound
 // the workspace whatever R * T is.  Larger chunks measured faster all the way to one launch
 // (cfg2's shape, 2272 rows, V = 4444: generator + tail 1.043 / 0.371 / 0.235 / 0.204 ms with

@@ -212,8 +212,30 @@ __device__ __forceinline__ int r_slot(int r, int c) { return c ^ ((r >> 1) & 7);
 // prefetched under the epilogue) and software-pipelined fragment reads: within noise —
 // the main loop is bound by the L2 -> LDS fill (~75 GB/s per CU), not by LDS latency or
 // workgroup turnover.
-template <int EPI, bool FULL, bool FAULT, bool KP>
-__global__ __launch_bounds__(512) void k_gemm_row(RowGemmArgs g) {
+// The table form (FAULT == 2, launch_gemm_row_tab): RowGemmArgs plus the per-row fault table of
+// the encoder trials decode, one RowFault per token row [M], and the (layer, gemm) this launch
+// computes.  The other instances take RowGemmArgs itself, so their kernel arguments stay.
+struct RowTabGemmArgs : RowGemmArgs {
+  const RowFault* tab;
+  int layer, gemm;
+};
+// The table's tile in LDS: st0's last 16 KB, which no epilogue touches (RE_RES_LN stages
+// 32 rows x 2 KB in each stage, the absmax reductions use st0's first 2 KB)
+constexpr int R_TAB_OFF = 64 * 1024;
+static_assert(R_TAB_OFF + R_BM * (int)sizeof(RowFault) + 16 <= R_STAGE, "the table tile fits st0");
+static_assert(R_TAB_OFF >= 32 * R_BN * (int)sizeof(float) && R_TAB_OFF >= 4 * R_BM * (int)sizeof(float),
+              "the table tile lies past RE_RES_LN's staging rows and the absmax reduction");
+
+template <int FAULT> struct RowArgsOf { using T = RowGemmArgs; };
+template <> struct RowArgsOf<2> { using T = RowTabGemmArgs; };
+
+// FAULT: 0 none (the product kernels), 1 the one fault of RowGemmArgs::fault, 2 the table
+// (row-major operands only): every output row takes the corrections of its own table entry, and
+// only where the entry names this (layer, gemm) launch — the single-fault expressions in the
+// same order (the exact int32 delta before the float epilogue, OUTPUT as value + bias before
+// ReLU), so a row equals the single-fault kernel's on that row alone.
+template <int EPI, bool FULL, int FAULT, bool KP>
+__global__ __launch_bounds__(512) void k_gemm_row(typename RowArgsOf<FAULT>::T g) {
   // one 160 KB LDS array: two 80 KB stages of 128-byte K steps (row-major operands) or
   // four 40 KB stages of 64-byte K steps (KP operands); the epilogues reuse it
   __shared__ __attribute__((aligned(16))) uint8_t lds[2 * R_STAGE];
@@ -421,7 +443,51 @@ __global__ __launch_bounds__(512) void k_gemm_row(RowGemmArgs g) {
       }
     return;
   } else {
-  if (FAULT && (g.fault.kind == FK_INPUT || g.fault.kind == FK_WEIGHT)) {
+  // ---- the table form: the tile's entries that name this launch, staged in LDS (free now);
+  // a tile without one skips every correction below (uniform branch) ---------------------
+  [[maybe_unused]] const RowFault* ft = nullptr;
+  [[maybe_unused]] bool ft_any = false;
+  if constexpr (FAULT == 2) {
+    RowFault* fts = reinterpret_cast<RowFault*>(lds + R_TAB_OFF);
+    int* fhit = reinterpret_cast<int*>(fts + R_BM);         // [2]: waves 0 and 1 stage
+    if (tid < R_BM) {
+      RowFault f{};
+      if (m0 + tid < g.M) f = g.tab[m0 + tid];
+      const bool hit = f.kind != FK_NONE && f.layer == g.layer && f.gemm == g.gemm;
+      if (!hit) f.kind = FK_NONE;
+      fts[tid] = f;
+      const unsigned long long any = __ballot(hit);
+      if (lane == 0) fhit[wave] = any != 0ull;
+    }
+    __syncthreads();
+    ft = fts;
+    ft_any = (fhit[0] | fhit[1]) != 0;
+    if (ft_any) {
+      // k_gemm_row's exact integer correction, per output row from the row's own entry
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int rl = wm * 64 + i * 16 + 4 * fg + e;
+          const RowFault f = ft[rl];
+          if (f.kind == FK_INPUT || f.kind == FK_WEIGHT) {     // (a staged entry: row < M)
+            const long row = m0 + rl;
+            const bool inp = f.kind == FK_INPUT;
+            const int8_t orig = inp ? g.A[row * g.lda + f.col] : g.W[(long)f.wrow * g.ldw + f.col];
+            const int delta = (int)(int8_t)(orig ^ (1 << f.bit)) - (int)orig;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const long col = n0 + wn * 128 + 8 * fr + j;
+              if (inp && col >= f.lo && col < f.hi)
+                acc[i][j][e] += delta * (int)g.W[col * g.ldw + f.col];
+              if (!inp && col == f.wrow)
+                acc[i][j][e] += delta * (int)g.A[row * g.lda + f.col];
+            }
+          }
+        }
+    }
+  }
+  if (FAULT == 1 && (g.fault.kind == FK_INPUT || g.fault.kind == FK_WEIGHT)) {
     // exact integer correction of the accumulators for one bit-flipped int8 operand
     // (the perturbation the reference propagates through the MatMul, inject_utils/layers.py)
     const FaultArgs& f = g.fault;
@@ -469,7 +535,27 @@ __global__ __launch_bounds__(512) void k_gemm_row(RowGemmArgs g) {
           y[i][j][e] = (EPI == RE_RELU_PMAX || EPI == RE_RELU_QUANT_PMAX) ? (v > 0.0f ? v : 0.0f) : v;
         }
       }
-    if (FAULT && g.fault.kind == FK_OUTPUT) {   // RANDOM fault models: one MatMul output value replaced
+    if constexpr (FAULT == 2) {
+      if (ft_any) {                               // the rows whose entry is an OUTPUT fault
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int rl = wm * 64 + i * 16 + 4 * fg + e;
+            if (ft[rl].kind == FK_OUTPUT) {
+              const int fcol = ft[rl].col;
+              const float fval = ft[rl].value;
+#pragma unroll
+              for (int j = 0; j < 8; ++j)
+                if (n0 + cl + j == fcol) {
+                  const float v = fval + bc[j];
+                  y[i][j][e] = (EPI == RE_RELU_PMAX || EPI == RE_RELU_QUANT_PMAX) ? (v > 0.0f ? v : 0.0f) : v;
+                }
+            }
+          }
+      }
+    }
+    if (FAULT == 1 && g.fault.kind == FK_OUTPUT) {   // RANDOM fault models: one MatMul output value replaced
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -772,19 +858,19 @@ hipError_t launch_gemm_row(const RowGemmArgs& g, hipStream_t st) {
     // split K: ksplit x the workgroups of a small M, then the row-wise epilogue
     if ((g.K / 64) % (4 * g.ksplit)) return hipErrorInvalidValue;
     const dim3 gs(grid.x, g.ksplit);
-    if (full) k_gemm_row<RE_PARTIAL, true, false, true><<<gs, block, 0, st>>>(g);
-    else k_gemm_row<RE_PARTIAL, false, false, true><<<gs, block, 0, st>>>(g);
+    if (full) k_gemm_row<RE_PARTIAL, true, 0, true><<<gs, block, 0, st>>>(g);
+    else k_gemm_row<RE_PARTIAL, false, 0, true><<<gs, block, 0, st>>>(g);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     k_res_ln_partials<<<dim3((g.M + 3) / 4), dim3(256), 0, st>>>(g);
     return hipGetLastError();
   }
 #define QTX_ROW_LAUNCH(E)                                                                      \
-  (g.fault.kind != FK_NONE ? (k_gemm_row<E, false, true, false><<<grid, block, 0, st>>>(g), 0)   \
-   : g.kp ? (full ? (k_gemm_row<E, true, false, true><<<grid, block, 0, st>>>(g), 0)             \
-                  : (k_gemm_row<E, false, false, true><<<grid, block, 0, st>>>(g), 0))            \
-   : full ? (k_gemm_row<E, true, false, false><<<grid, block, 0, st>>>(g), 0)                    \
-          : (k_gemm_row<E, false, false, false><<<grid, block, 0, st>>>(g), 0))
+  (g.fault.kind != FK_NONE ? (k_gemm_row<E, false, 1, false><<<grid, block, 0, st>>>(g), 0)   \
+   : g.kp ? (full ? (k_gemm_row<E, true, 0, true><<<grid, block, 0, st>>>(g), 0)             \
+                  : (k_gemm_row<E, false, 0, true><<<grid, block, 0, st>>>(g), 0))            \
+   : full ? (k_gemm_row<E, true, 0, false><<<grid, block, 0, st>>>(g), 0)                    \
+          : (k_gemm_row<E, false, 0, false><<<grid, block, 0, st>>>(g), 0))
   switch (g.epi) {
     case RE_QUANT: QTX_ROW_LAUNCH(RE_QUANT); break;
     case RE_RES_LN: QTX_ROW_LAUNCH(RE_RES_LN); break;
@@ -793,6 +879,32 @@ hipError_t launch_gemm_row(const RowGemmArgs& g, hipStream_t st) {
     default: return hipErrorInvalidValue;
   }
 #undef QTX_ROW_LAUNCH
+  return hipGetLastError();
+}
+
+hipError_t launch_gemm_row_tab(const RowGemmArgs& a, const RowFault* tab, int layer, int gemm,
+                               hipStream_t st) {
+  if (!tab) return launch_gemm_row(a, st);        // the no-fault instance: bit-identical
+  if (a.M <= 0) return hipSuccess;
+  if (a.kp || a.fault.kind != FK_NONE || a.N % R_BN || a.K % R_BK || a.K <= 0 || (a.lda % 16) ||
+      (a.ldw % 16) || (a.epi == RE_RES_LN && a.N != R_BN))
+    return hipErrorInvalidValue;
+  RowTabGemmArgs g{};
+  static_cast<RowGemmArgs&>(g) = a;
+  g.tab = tab; g.layer = layer; g.gemm = gemm;
+  const dim3 grid((g.N / R_BN) * ((g.M + R_BM - 1) / R_BM)), block(512);
+  const bool full = g.M % R_BM == 0;
+#define QTX_TAB_LAUNCH(E)                                                 \
+  (full ? (k_gemm_row<E, true, 2, false><<<grid, block, 0, st>>>(g), 0)         \
+        : (k_gemm_row<E, false, 2, false><<<grid, block, 0, st>>>(g), 0))
+  switch (g.epi) {
+    case RE_QUANT: QTX_TAB_LAUNCH(RE_QUANT); break;
+    case RE_RES_LN: QTX_TAB_LAUNCH(RE_RES_LN); break;
+    case RE_RELU_PMAX: QTX_TAB_LAUNCH(RE_RELU_PMAX); break;
+    case RE_RELU_QUANT_PMAX: QTX_TAB_LAUNCH(RE_RELU_QUANT_PMAX); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef QTX_TAB_LAUNCH
   return hipGetLastError();
 }
 

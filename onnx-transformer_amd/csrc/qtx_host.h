@@ -1,5 +1,5 @@
 // qtx_host.h — what the C-ABI's host sources (qtx_model.hip, qtx_api.hip, qtx_fault.hip,
-// qtx_trials.hip, qtx_search.hip, qtx_ops.hip) share, internal to libqtx: the model handle, the
+// qtx_trials.hip, qtx_enctrials.hip, qtx_search.hip, qtx_ops.hip) share, internal to libqtx: the model handle, the
 // error and status helpers, the frame and the argument rules of a model-level entry, and the
 // stack and decode-step helpers that cross files.  Host code only: no kernel in any of them.
 #pragma once
@@ -186,6 +186,11 @@ inline int check_workspace(size_t ws_bytes, size_t need) {
   return ws_bytes < need ? fail(QTX_E_WORKSPACE, "workspace too small") : QTX_OK;
 }
 
+// qtx_row_gemm as the kernels' RowGemmArgs with qtx_linear_rows' argument rules (qtx_ops.hip;
+// qtx_linear_rows_faults, qtx_enctrials.hip, applies the same)
+int row_gemm_args(const qtx_row_gemm* a, RowGemmArgs* g);
+int launched(hipError_t e, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
 // ---- stack building blocks (qtx_api.hip) --------------------------------------------------
 RowArgs rows_quant(const float* x, long ldx, int rows, int D, int8_t* q, float* s);
 int ln_quant(const float* x, int rows, const float* const* ln, int D, int8_t* q, float* s,
@@ -216,6 +221,19 @@ int check_fault(const qtx_model* m, const qtx_fault* f, int module, long B, long
                 long self_keys = 0, long w_window = 0);
 // whether f sits in a memory K / V projection (the fault then needs its own cross K/V)
 bool ckv_fault(const qtx_model* m, const qtx_fault* f, int Ms);
+
+// the row-complete chain's pieces the encoder trials decode shares (qtx_api.hip)
+bool row_path(const qtx_config& c);
+RowGemmArgs rowgemm(const QLin& L, const int8_t* a8, const float* sa, int M, int epi, bool kp);
+int attention_quant(const AttnArgs& a, const AttnFault* af, int M, int D, Scratch& s, bool kp,
+                    hipStream_t st);
+// linear() at any M on the row-fault GEMM, every row with its own table entry (qtx_trials.hip)
+int rf_linear(const QLin& L, const int8_t* a8, const float* sa, int M, int flags, const float* res,
+              float* out, long ldo, const RowFault* tab, int t, int l, GemmId gid, hipStream_t st);
+// The refusal of row b, with the row in its text (qtx_trials.hip)
+int named(int rc, int b);
+// the steps of a greedy decode after greedy_prologue (greedy_run's path selection)
+int greedy_steps(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, hipStream_t st);
 
 // ---- the stacks and the decode steps (qtx_api.hip) ----------------------------------------
 int encoder_run(const qtx_model* m, const float* x, const uint8_t* mask, int B, int S,

@@ -306,6 +306,13 @@ struct RowFault {
 // tab [g.M] (null: no faults).  The caller bounds every entry's col / wrow / lo / hi on the host.
 hipError_t launch_gemm_rowfault(const GemmArgs& g, const RowFault* tab, int step, int layer,
                                 int gemm, hipStream_t st);
+// k_gemm_row_tab (qtx_gemm.hip): launch_gemm_row's row-major form (a.kp == 0, a.fault unused)
+// at M = B * S with one RowFault per token row, tab [a.M]: each output row takes its own entry's
+// corrections where the entry names (layer, gemm); RowFault::step is not read.  For FK_WEIGHT the
+// host writes the entry into every row of the sentence inside the fault's window.  tab null: the
+// plain launch_gemm_row.  The caller bounds every entry's col / wrow / lo / hi on the host.
+hipError_t launch_gemm_row_tab(const RowGemmArgs& a, const RowFault* tab, int layer, int gemm,
+                               hipStream_t st);
 // k_trial_record: rec[b][which][:] = entry (b, step) of top_ids / top_logp [B][top_bs][2] for the
 // rows with tstep[b] == step; every other row of rec stays.
 hipError_t launch_trial_record(const int64_t* top_ids, const float* top_logp, long top_bs,

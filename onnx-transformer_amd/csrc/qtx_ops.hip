@@ -40,6 +40,46 @@ AttnArgs dense_attn_args(const int8_t* q, const float* sq, const int8_t* k, cons
   return a;
 }
 
+// qtx_row_gemm as the kernels' RowGemmArgs, with every argument rule of qtx_linear_rows
+int row_gemm_args(const qtx_row_gemm* a, RowGemmArgs* g) {
+  if (!a || !a->A || !a->sa || !a->W || !a->sw || !a->bias) return fail(QTX_E_INVALID, "null argument");
+  g->A = a->A; g->lda = a->K; g->sa = a->sa; g->W = a->W; g->ldw = a->K; g->sw = a->sw;
+  g->bias = a->bias; g->M = a->M; g->N = a->N; g->K = a->K; g->epi = a->epi;
+  g->out8 = a->out8; g->ldo8 = a->ldo8; g->o8_ts = a->o8_ts; g->os = a->os; g->os_ts = a->os_ts;
+  g->res = a->res; g->xout = a->xout; g->ln_a = a->ln_a; g->ln_b = a->ln_b;
+  g->lnq = a->lnq; g->lns = a->lns; g->lnout = a->lnout;
+  g->pmax_out = a->pmax_out; g->pmax_in = a->pmax_in; g->pmax_n = a->pmax_n; g->kp = a->kp;
+  g->status = reinterpret_cast<unsigned*>(a->status);
+  g->part = a->part; g->ksplit = a->ksplit;
+  if (g->ksplit > 1 && (g->epi != RE_RES_LN || g->kp != 1 || !g->part || (g->ksplit & (g->ksplit - 1)) ||
+                       g->ksplit > 8))
+    return fail(QTX_E_INVALID, "ksplit %d: epi 1 with kp 1, a power of two <= 8, and part", g->ksplit);
+  if (g->ksplit > 1 && (g->K % 64 || (g->K / 64) % (4 * g->ksplit)))   // launch_gemm_row's split
+    return fail(QTX_E_INVALID, "ksplit %d needs K / 64 a multiple of 4 * ksplit (K=%d)", g->ksplit, g->K);
+  const bool ok = (g->epi == RE_QUANT && g->out8 && g->os) ||
+                  (g->epi == RE_RES_LN && g->res && g->xout && g->ln_a && g->ln_b &&
+                   (g->lnq ? g->lns != nullptr : g->lnout != nullptr)) ||
+                  (g->epi == RE_RELU_PMAX && g->pmax_out) ||
+                  (g->epi == RE_RELU_QUANT_PMAX && g->out8 && g->os &&
+                   (g->kp == 3 || g->kp == 5 ? g->pmax_out != nullptr : (g->pmax_in && g->pmax_n > 0)));
+  if (!ok) return fail(QTX_E_INVALID, "operands missing for epi %d", g->epi);
+  // A, W and out8 move in 16-byte vectors (k_gemm_row: plain stores; the WS kernels: buffer
+  // stores through a descriptor of M * ldo8 bytes), so their bases and the out8 strides must
+  // be multiples of 16 and a row must hold its tile — checked here, before any launch
+  if (!aligned16(g->A) || !aligned16(g->W))
+    return fail(QTX_E_INVALID, "A / W must be 16-byte aligned");
+  if (g->epi == RE_QUANT || g->epi == RE_RELU_QUANT_PMAX) {
+    const long row = g->epi == RE_QUANT ? 512 : g->N;
+    if (!aligned16(g->out8) || g->ldo8 < row || g->ldo8 % 16 || (g->kp && g->epi != RE_QUANT && g->ldo8 % 64))
+      return fail(QTX_E_INVALID, "out8 must be 16-byte aligned with ldo8 %% 16 == 0 (KP: %% 64) "
+                                 "and ldo8 >= %ld (ldo8=%ld)", row, (long)g->ldo8);
+    if (g->epi == RE_QUANT && (g->o8_ts % 16 || g->o8_ts < 0 || g->os_ts < 0))
+      return fail(QTX_E_INVALID, "o8_ts must be a non-negative multiple of 16, os_ts >= 0 "
+                                 "(o8_ts=%ld os_ts=%ld)", (long)g->o8_ts, (long)g->os_ts);
+  }
+  return QTX_OK;
+}
+
 }  // namespace qtx
 
 using namespace qtx;
@@ -120,42 +160,8 @@ int32_t qtx_linear_i8(const int8_t* A, const float* sa, const void* W, const flo
 }
 
 int32_t qtx_linear_rows(const qtx_row_gemm* a, void* stream) {
-  if (!a || !a->A || !a->sa || !a->W || !a->sw || !a->bias) return fail(QTX_E_INVALID, "null argument");
   RowGemmArgs g{};
-  g.A = a->A; g.lda = a->K; g.sa = a->sa; g.W = a->W; g.ldw = a->K; g.sw = a->sw;
-  g.bias = a->bias; g.M = a->M; g.N = a->N; g.K = a->K; g.epi = a->epi;
-  g.out8 = a->out8; g.ldo8 = a->ldo8; g.o8_ts = a->o8_ts; g.os = a->os; g.os_ts = a->os_ts;
-  g.res = a->res; g.xout = a->xout; g.ln_a = a->ln_a; g.ln_b = a->ln_b;
-  g.lnq = a->lnq; g.lns = a->lns; g.lnout = a->lnout;
-  g.pmax_out = a->pmax_out; g.pmax_in = a->pmax_in; g.pmax_n = a->pmax_n; g.kp = a->kp;
-  g.status = reinterpret_cast<unsigned*>(a->status);
-  g.part = a->part; g.ksplit = a->ksplit;
-  if (g.ksplit > 1 && (g.epi != RE_RES_LN || g.kp != 1 || !g.part || (g.ksplit & (g.ksplit - 1)) ||
-                       g.ksplit > 8))
-    return fail(QTX_E_INVALID, "ksplit %d: epi 1 with kp 1, a power of two <= 8, and part", g.ksplit);
-  if (g.ksplit > 1 && (g.K % 64 || (g.K / 64) % (4 * g.ksplit)))   // launch_gemm_row's split
-    return fail(QTX_E_INVALID, "ksplit %d needs K / 64 a multiple of 4 * ksplit (K=%d)", g.ksplit, g.K);
-  const bool ok = (g.epi == RE_QUANT && g.out8 && g.os) ||
-                  (g.epi == RE_RES_LN && g.res && g.xout && g.ln_a && g.ln_b &&
-                   (g.lnq ? g.lns != nullptr : g.lnout != nullptr)) ||
-                  (g.epi == RE_RELU_PMAX && g.pmax_out) ||
-                  (g.epi == RE_RELU_QUANT_PMAX && g.out8 && g.os &&
-                   (g.kp == 3 || g.kp == 5 ? g.pmax_out != nullptr : (g.pmax_in && g.pmax_n > 0)));
-  if (!ok) return fail(QTX_E_INVALID, "operands missing for epi %d", g.epi);
-  // A, W and out8 move in 16-byte vectors (k_gemm_row: plain stores; the WS kernels: buffer
-  // stores through a descriptor of M * ldo8 bytes), so their bases and the out8 strides must
-  // be multiples of 16 and a row must hold its tile — checked here, before any launch
-  if (!aligned16(g.A) || !aligned16(g.W))
-    return fail(QTX_E_INVALID, "A / W must be 16-byte aligned");
-  if (g.epi == RE_QUANT || g.epi == RE_RELU_QUANT_PMAX) {
-    const long row = g.epi == RE_QUANT ? 512 : g.N;
-    if (!aligned16(g.out8) || g.ldo8 < row || g.ldo8 % 16 || (g.kp && g.epi != RE_QUANT && g.ldo8 % 64))
-      return fail(QTX_E_INVALID, "out8 must be 16-byte aligned with ldo8 %% 16 == 0 (KP: %% 64) "
-                                 "and ldo8 >= %ld (ldo8=%ld)", row, (long)g.ldo8);
-    if (g.epi == RE_QUANT && (g.o8_ts % 16 || g.o8_ts < 0 || g.os_ts < 0))
-      return fail(QTX_E_INVALID, "o8_ts must be a non-negative multiple of 16, os_ts >= 0 "
-                                 "(o8_ts=%ld os_ts=%ld)", (long)g.o8_ts, (long)g.os_ts);
-  }
+  RC(row_gemm_args(a, &g));
   return launched(g.kp == 3 || g.kp == 5 ? launch_gemm_wsx(g, (hipStream_t)stream)
                        : g.kp == 2 || g.kp == 4 ? launch_gemm_ws(g, (hipStream_t)stream)
                                    : launch_gemm_row(g, (hipStream_t)stream),

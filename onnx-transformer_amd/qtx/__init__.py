@@ -11,6 +11,8 @@ Public surface mirrors the reference's entry points:
                                                KV-cached decode itself (no reference counterpart)
   greedy_decode_kvfault_trials(model, src, src_mask, max_len, start_symbol, trials)   one such
                                                trial per sentence in one decode; kvfault_campaign
+  greedy_decode_enctrials(model, src, src_mask, max_len, start_symbol, faults)   one encoder or
+                                               memory K/V fault per sentence; encfault_campaign
   score_targets(model, src, src_mask, tgt) -> TargetScores   ~ EncoderDecoder.forward on a given
                                                                target + log_softmax
 """
@@ -21,7 +23,8 @@ __all__ = ["BOS", "EOS", "PAD", "UNK", "DEFAULT_SEED", "ModelConfig", "load_chec
            "positional_table", "synthetic_state_dict", "tensor_order", "QtxModel",
            "InferenceSession", "run_module", "set_default_model", "greedy_decode",
            "greedy_decode_fault", "greedy_decode_kvfault", "greedy_decode_kvfault_trials",
-           "kvfault_campaign", "decode_fault_sweep", "plan_sweep",
+           "kvfault_campaign", "greedy_decode_enctrials", "encfault_campaign",
+           "decode_fault_sweep", "plan_sweep",
            "SweepStats", "Scores", "FaultStepRecord", "make_src_mask", "score_targets",
            "rescore_beam", "TargetScores", "lib"]
 
@@ -35,7 +38,8 @@ def __getattr__(name):
         from . import session
         return getattr(session, name)
     if name in ("greedy_decode", "greedy_decode_fault", "greedy_decode_kvfault",
-                "greedy_decode_kvfault_trials", "kvfault_campaign",
+                "greedy_decode_kvfault_trials", "kvfault_campaign", "greedy_decode_enctrials",
+                "encfault_campaign",
                 "decode_fault_sweep", "plan_sweep", "SweepStats", "Scores", "FaultStepRecord",
                 "make_src_mask", "score_targets", "rescore_beam", "TargetScores"):
         from . import decode

@@ -15,7 +15,7 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "libqtx.so")
 SOURCES = ["qtx_kernels.hip", "qtx_decode.hip", "qtx_gemm.hip", "qtx_wsgemm.hip", "qtx_attn.hip",
            "qtx_ffn.hip", "qtx_model.hip", "qtx_api.hip", "qtx_fault.hip", "qtx_search.hip",
-           "qtx_ops.hip", "qtx_knobs.hip", "qtx_rowfault.hip", "qtx_trials.hip"]
+           "qtx_ops.hip", "qtx_knobs.hip", "qtx_rowfault.hip", "qtx_trials.hip", "qtx_enctrials.hip"]
 # measured-negative kernel variants and their switches: compiled only into the diagnostic
 # library (build(extra=...) -> libqtx_diag.so, with -DQTX_DIAG), never into libqtx.so
 DIAG_SOURCES = ["diag/qtx_wsgemm_diag.hip"]   # csrc/diag/: outside the product sources
@@ -49,6 +49,7 @@ def hipcc() -> str:
 def _inputs():
     files = [os.path.join(CSRC, s) for s in SOURCES + HEADERS]
     files.append(os.path.join(REPO, "include", "qtx.h"))
+    files.append(os.path.join(REPO, "include", "qtx_enctrials.h"))
     files.append(os.path.abspath(__file__))
     return files
 

@@ -67,6 +67,12 @@ class KvTrial(C.Structure):
     _fields_ = [("what", I32), ("step", I32), ("fault", Fault), ("upset", CacheUpset)]
 
 
+class RowFault(C.Structure):
+    """struct qtx_row_fault (include/qtx_enctrials.h)."""
+    _fields_ = [("step", I32), ("layer", I32), ("gemm", I32), ("kind", I32), ("bit", I32),
+                ("col", I32), ("wrow", I32), ("lo", I32), ("hi", I32), ("value", F32)]
+
+
 FP = C.POINTER(Fault)
 UP = C.POINTER(CacheUpset)
 TP = C.POINTER(KvTrial)
@@ -141,6 +147,13 @@ SIGNATURES = {
     "qtx_model_check": (I32, [P, P]),
 }
 
+# the same for include/qtx_enctrials.h
+SIGNATURES_ENCTRIALS = {
+    "qtx_linear_rows_faults": (I32, [C.POINTER(RowGemm), C.POINTER(RowFault), I32, I32, P]),
+    "qtx_greedy_enctrials_workspace_size": (SZ, [P, I32, I32, I32]),
+    "qtx_greedy_decode_enctrials": (I32, [P, P, P, I32, I32, I32, I64, P, P, P, P, SZ, FP, P]),
+}
+
 
 def header_symbols(path=None) -> list[str]:
     """Function names declared in include/qtx.h (used by the ABI test)."""
@@ -160,7 +173,7 @@ def lib(build: bool = True):
     if not os.path.exists(path):
         raise RuntimeError(f"libqtx.so missing at {path}; run __graft_entry__.build()")
     L = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **SIGNATURES_ENCTRIALS}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     _lib = L

@@ -400,6 +400,52 @@ def kvfault_campaign(model: QtxModel, src_row, mask_row, max_len: int, trials, b
     return out
 
 
+def greedy_decode_enctrials(model: QtxModel, src, src_mask, max_len: int, start_symbol: int = 0,
+                            faults=()):
+    """One scored greedy decode that carries one independent encoder-side fault per sentence
+    (qtx_greedy_decode_enctrials; the contract is tests/enctrials_ref.py): ``faults`` is a list of
+    B items, each None (a golden row) or a Fault in the coordinates of the stand-alone call on
+    that sentence ALONE — an encoder fault (module 0: Q K V O FFN1 FFN2 QK PV) as
+    greedy_decode(.., fault=, return_scores=True) takes it, or a decoder CK / CV fault as
+    greedy_decode_kvfault takes it at step 0: linear INPUT / OUTPUT row = the token in [0, S),
+    attention b = 0 with Sq = Sk = S.  Row b equals that stand-alone call bit for bit.
+    fault.random_fault(.., rows=S) and fault.random_attn_fault(.., B=1, ..) draw in these
+    coordinates.  Returns (ys int64 [B, max_len], Scores)."""
+    import torch
+    src = np.ascontiguousarray(np.asarray(src), np.int64)
+    B, S = src.shape
+    srcd = torch.from_numpy(src).to(model.device)
+    md = to_u8_mask(src_mask, model.device).reshape(B, S)
+    ys, top_ids, top_logp = model.greedy_enctrials(srcd, md, list(faults), max_len=max_len,
+                                                   start=start_symbol)
+    model.check()
+    return ys.cpu().numpy(), Scores(top_ids.cpu().numpy(), top_logp.cpu().numpy())
+
+
+def encfault_campaign(model: QtxModel, src_row, mask_row, max_len: int, faults, batch: int = 32,
+                      start_symbol: int = 0):
+    """A campaign of encoder-side trials on ONE sentence, the twin of kvfault_campaign: src_row
+    [S] (or [1, S]) and its mask row are replicated over ``batch`` rows, ``faults`` (any number
+    of Fault or None, in greedy_decode_enctrials' coordinates) are cut into batches of ``batch``
+    — the last padded with None — and each batch is one greedy_decode_enctrials call.  Returns
+    one (ys [max_len], Scores with arrays [max_len-1, 2]) per trial, in the caller's order."""
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    faults = list(faults)
+    src = np.repeat(np.asarray(src_row, np.int64).reshape(1, -1), batch, axis=0)
+    S = src.shape[1]
+    mask = np.repeat((np.asarray(mask_row) != 0).reshape(1, 1, S), batch, axis=0)
+    out = []
+    for k in range(0, len(faults), batch):
+        chunk = faults[k:k + batch]
+        ys, sc = greedy_decode_enctrials(model, src, mask, max_len, start_symbol,
+                                         chunk + [None] * (batch - len(chunk)))
+        out += [(ys[b].copy(), Scores(sc.top_ids[b].copy(), sc.top_logp[b].copy()))
+                for b in range(len(chunk))]
+    return out
+
+
 @dataclasses.dataclass
 class SweepStats:
     """decode_fault_sweep's counts: trials in all; ``n_resumed`` whose fault changed a token,

@@ -139,7 +139,9 @@ def random_attn_fault(rng, kind, module, layer, linear, B, Sq, Sk, H=8, bit=None
     tensor (q / P*127 input, k / v weight, [B, H, S, .]), INPUT16 a 16-aligned window of the
     output's last dim (keys for QK^T, head dims for PV), WEIGHT16 a 16-aligned start and
     1..15 query rows (onnx_optimized_inference.py:121-186).  golden_output for
-    RANDOM_BITFLIP: the golden MatMul output [B, H, Sq, Sk|64]."""
+    RANDOM_BITFLIP: the golden MatMul output [B, H, Sq, Sk|64].
+    With module 0 and B = 1, Sq = Sk = S the draw is in the coordinates of one sentence's
+    trial of decode.greedy_decode_enctrials."""
     qk = linear in ("QK", "CQK")
     f = Fault(kind, module, layer, linear, bit=0 if bit is None else int(bit))
     b, h = int(rng.integers(B)), int(rng.integers(H))
@@ -177,7 +179,9 @@ def random_fault(rng, kind, module, layer, linear, rows, bit=None, d_model=512, 
     16-aligned window for the *16 kinds (onnx_optimized_inference.py:123-131, 157-166:
     INPUT16 keeps 16 columns, WEIGHT16 a random 1..15 rows), a random fp32 for RANDOM
     (delta_init) and one flipped bit of the golden output for RANDOM_BITFLIP
-    (float32_bit_flip; golden_output [rows, N] host array required)."""
+    (float32_bit_flip; golden_output [rows, N] host array required).
+    With rows = S (module 0, or module 1 with CK / CV) the draw is in the coordinates of one
+    sentence's trial of decode.greedy_decode_enctrials."""
     N, K = linear_shape(linear, d_model, d_ff)
     f = Fault(kind, module, layer, linear, bit=0 if bit is None else int(bit))
     if kind in ("INPUT", "INPUT16"):

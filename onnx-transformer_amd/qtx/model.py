@@ -337,6 +337,26 @@ class QtxModel:
         return ids, top_ids, top_logp, rec_ids, rec_logp
 
     @_on_device
+    def greedy_enctrials(self, src, src_mask_u8, faults, max_len: int = 72, start: int = 0):
+        """One scored greedy decode with one encoder-side fault per sentence
+        (qtx_greedy_decode_enctrials, include/qtx_enctrials.h).  faults: B items, each None or a
+        qtx.fault.Fault — an encoder fault, or a decoder CK / CV fault — in the coordinates of
+        the B = 1 call on that sentence.  Returns (ids, top_ids, top_logp) on the device."""
+        B, S = src.shape
+        if len(faults) != B:
+            raise ValueError(f"{len(faults)} faults for {B} sentences")
+        arr = (_lib.Fault * B)()
+        for b, f in enumerate(faults):
+            if f is not None:
+                arr[b] = f.to_c()
+        ids, top_ids, top_logp, _, _ = self._dfault_outputs(B, max_len, True)
+        ws = self.workspace(_lib.lib().qtx_greedy_enctrials_workspace_size(self.handle, B, S, max_len))
+        _lib.call("qtx_greedy_decode_enctrials", self.handle, _ptr(src), _ptr(src_mask_u8), B, S,
+                  max_len, int(start), _ptr(ids), _ptr(top_ids), _ptr(top_logp), _ptr(ws),
+                  ws.numel(), arr, _stream(self.device))
+        return ids, top_ids, top_logp
+
+    @_on_device
     def embed(self, ids, which: str = "src", pos0: int = 0):
         torch = _torch()
         B, T = ids.shape

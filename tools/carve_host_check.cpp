@@ -305,6 +305,22 @@ static void decode_case(const qtx_config& c, const Groups& gr, int B, int S, int
     r.add("pair_logp", w.pair_logp, (size_t)B * 4);
     r.verify(b.ar.base, bytes);
   }
+  {   // the encoder trials decode: the scored greedy decode a prefix, then the token-row table
+    const size_t bytes = enctrials_ws(c, gr, B, S, max_len);
+    CHECK(bytes >= z.scored);
+    Block b(bytes);
+    const EnctrialsWS w = carve_enctrials(b.ar, c, gr, B, S, max_len);
+    b.spent();
+    Arena again;
+    again.base = b.ar.base; again.cap = z.scored;
+    const GreedyWS g = carve_greedy(again, c, gr, B, S, max_len, true);
+    same_greedy(g, w.g);
+    CHECK(g.top_ids == w.g.top_ids && g.top_logp == w.g.top_logp && !w.g.no_fold);
+    Regions r;
+    add_greedy(r, w.g, c, gr, B, S, max_len, true);
+    r.add("tab", w.tab, (size_t)B * S * 10);
+    r.verify(b.ar.base, bytes);
+  }
 }
 
 static void score_case(const qtx_config& c, int B, int S, int T, int K, int nf) {
