@@ -78,7 +78,9 @@ def model97(torch):
 @pytest.mark.parametrize("B", [1, 3, 5, 33, 97])
 def test_fold_batch_sizes(torch, model97, knob_env, B):
     """B = 1, 3, 5: a ragged 4-row block; 33: two 16-row generator blocks and a ragged third;
-    97: the 8-row instances (two rows per wave), the last block ragged."""
+    97: the 8-row instances (two rows per wave), the last block ragged.  This model has two
+    layers, d_ff 512 and 97 words; tests/test_gpu_wide_batch.py decodes 97 and 193 rows on the
+    default model (4444 words, the d_ff 2048 FFN2)."""
     gm, om = model97
     src, m = MC.small_src(B, S, 11 + B, full=(0,))
     ref = memo(("b", B), lambda: om.greedy_decode(src, m, L))
