@@ -77,12 +77,15 @@ typedef struct qtx_model qtx_model;
  * Every config qtx_model_create accepts runs every model-level call (tests/
  * test_gpu_model_configs.py; the kernel chain per config: DESIGN.md, supported shapes):
  * the row-GEMM encoder / decoder chain needs d_ff % 512 == 0, the fused decode step
- * d_ff 512 or 2048, tgt_vocab <= 8192 and S, max_len <= 128; any other config or length takes
- * the generic chain and the unfused step, with the same results.
+ * d_ff 512 or 2048 and tgt_vocab <= 8192; any other config takes the generic chain and the
+ * unfused step, with the same results.
  * max_len: the rows of the positional table.  Every decoder-side entry takes up to 512 target
- * positions and never more than the table holds (the same for S); 129 .. 512 positions run
- * the unfused step and the generic attention kernel (supported shapes;
- * tests/test_gpu_long_target.py). */
+ * positions and never more than the table holds (the same for S).  qtx_greedy_decode and
+ * qtx_greedy_decode_scored run the fused step and its graphs at every such shape (past 128
+ * keys with the four-wave attention kernel, qtx_decode_attention below); the fault, trials,
+ * beam and score drivers run the fused step up to S, max_len <= 128 and the unfused step and
+ * the generic attention kernel from 129 on (supported shapes;
+ * tests/test_gpu_long_fused.py, tests/test_gpu_long_target.py). */
 typedef struct {
   int32_t src_vocab, tgt_vocab, n_layers, d_model, d_ff, n_heads, max_len, weight_bits;
 } qtx_config;
@@ -750,15 +753,15 @@ int32_t qtx_skinny_linear(int32_t amode, const int8_t* A, const float* sa, const
 /* One-query-per-sentence attention of the decode step (attention.py:23-67).
  * kv_new = 1 (self): y [B, 3*512] holds this step's q|k|v projections; they are quantized
  *   per token, k/v written to the caches at row b*kv_bs + *step_dev, keys 0..*step_dev
- *   (kv_bs <= 128).
+ *   (kv_bs <= 512).
  * kv_new = 0 (cross): y [B,512] holds q; keys = S cached rows per sentence, mask [B,S].
  * Caches: kc int8 [B][kv_bs][512]; vc int8 in groups of 4 keys, [B][ceil(kv_bs/4)][512][4]
  *   (byte ((b*G4 + j/4)*512 + d)*4 + j%4 holds v[b][j][d]: one dword = 4 keys of one dim);
  *   skc/svc [B][kv_bs].  Out: fp32 context ctx [B,512]
  * and the per-head absmax pmax [8][B] (the next GEMM's per-token quantization, amode 2 of
- * qtx_skinny_linear with pmax_n = 8).  Keys <= 128: this is the fused step's kernel; a decode
- * with S or max_len above 128 runs the unfused step, whose attention takes up to 512 keys
- * (qtx_attention_i8's kernel with the key count read from the step counter).  The PV MatMul
+ * qtx_skinny_linear with pmax_n = 8).  Keys <= 512 (S, kv_bs above: QTX_E_INVALID): the fused
+ * step's kernels — one wave per (sentence, head) up to kv_bs (self) or S (cross) = 128, four
+ * waves from 129 on, with the same results wherever both apply.  The PV MatMul
  * runs in the decoder's
  * canonical order (four partial chains; qtx_attention_i8 with dec = 1).
  * y rows are ldy floats apart (ldy >= the row width, ldy % 4 == 0; y, kc and vc 16-byte

@@ -542,7 +542,7 @@ Groups decode_groups(int B) {   // (Groups / split_groups, no empty group: qtx_c
   return split_groups(B, knobs().decode_groups > 0 ? knobs().decode_groups : B >= 512 ? 2 : 1);
 }
 
-// ---- fused decode step (M = B rows, keys <= 128) ----------------------------------------
+// ---- fused decode step (M = B rows, keys <= 512) ----------------------------------------
 // Its kernels exist for the flagship shapes only: the skinny GEMM takes K = 512 or 2048
 // (FFN2: K = d_ff; launch_skinny) and the argmax / top-2 tails a vocabulary of at most
 // ARG_MAXV.  Every other config qtx_model_create accepts decodes with the unfused step,
@@ -838,9 +838,15 @@ int decoder_body(const qtx_model* m, Scratch& s, const CrossKV& x, const uint8_t
   return QTX_OK;
 }
 
-// whether the decode runs the fused step (else the unfused one)
+// whether the decode runs the fused step (else the unfused one): the fault, trials, beam and
+// score drivers, whose own attention kernels and cache handling stop at 128 keys
 bool greedy_fused(const qtx_config& c, int S, int max_len) {
   return S <= 128 && max_len <= 128 && fused_step_ok(c) && !knobs().unfused;
+}
+// the same for the plain and the scored greedy decode, whose step needs nothing but
+// launch_dec_attn past 128 keys: every decode shape (k_dec_attn_long from key 129 on)
+bool greedy_fused_long(const qtx_config& c, int S, int max_len) {
+  return S <= 512 && max_len <= 512 && fused_step_ok(c) && !knobs().unfused;
 }
 
 int regroup_cross_values(const qtx_config& c, const CrossKV& x, int B, int S, int8_t* cvg,
@@ -905,9 +911,12 @@ StepRequest step_request(const qtx_model* m, std::vector<GreedyWS>& gv, const Gr
 
 // The steps of a greedy decode after its prologue, with the decode's path selection (the plain
 // or, with g.top_ids, the scored step).
-int greedy_steps(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, hipStream_t st) {
+// fused: the caller's path decision, the one its prologue was run with (the fused step reads
+// the cross values regrouped there: greedy_fused_long for the plain / scored decode,
+// greedy_fused for enctrials)
+int greedy_steps(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, bool fused,
+                 hipStream_t st) {
   const qtx_config& c = m->cfg;
-  const bool fused = greedy_fused(c, S, max_len);
   if (!fused) {
     for (int t = 0; t + 1 < max_len; ++t) RC(greedy_step_unfused(m, g, B, S, max_len, g.ids, g.mask, st));
     return QTX_OK;
@@ -938,8 +947,9 @@ int greedy_steps(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, hip
 
 int greedy_run(const qtx_model* m, GreedyWS& g, const int64_t* src, int B, int S, int max_len,
                int64_t start, const qtx_fault* f, hipStream_t st) {
-  RC(greedy_prologue(m, g, src, B, S, max_len, start, f, greedy_fused(m->cfg, S, max_len), st));
-  return greedy_steps(m, g, B, S, max_len, st);
+  const bool fused = greedy_fused_long(m->cfg, S, max_len);
+  RC(greedy_prologue(m, g, src, B, S, max_len, start, f, fused, st));
+  return greedy_steps(m, g, B, S, max_len, fused, st);
 }
 
 }  // namespace qtx

@@ -231,7 +231,7 @@ int32_t qtx_greedy_decode_enctrials(const qtx_model* m, const int64_t* src, cons
   // ids[:, 0] = start and the step counters (greedy_prologue), then the golden scored steps
   HIPCHK(launch_fill_col(g.ids, max_len, B, start, st));
   HIPCHK(launch_zero(g.step, 16, st));
-  RC(greedy_steps(m, g, B, S, max_len, st));
+  RC(greedy_steps(m, g, B, S, max_len, fused, st));
   return copy_out(g.ids, g.top_ids, g.top_logp, B, max_len, ids, top_ids, top_logp, st);
 }
 

@@ -233,7 +233,8 @@ int rf_linear(const QLin& L, const int8_t* a8, const float* sa, int M, int flags
 // The refusal of row b, with the row in its text (qtx_trials.hip)
 int named(int rc, int b);
 // the steps of a greedy decode after greedy_prologue (greedy_run's path selection)
-int greedy_steps(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, hipStream_t st);
+int greedy_steps(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, bool fused,
+                 hipStream_t st);
 
 // ---- the stacks and the decode steps (qtx_api.hip) ----------------------------------------
 int encoder_run(const qtx_model* m, const float* x, const uint8_t* mask, int B, int S,
@@ -246,6 +247,7 @@ int decoder_body(const qtx_model* m, Scratch& s, const CrossKV& x, const uint8_t
                  const qtx_fault* f, hipStream_t st);
 Groups decode_groups(int B);
 bool greedy_fused(const qtx_config& c, int S, int max_len);   // the fused step, else the unfused
+bool greedy_fused_long(const qtx_config& c, int S, int max_len);   // plain / scored greedy: to 512 keys
 // k_dec_attn's arguments for layer l's cached self / cross attention on g's step scratch
 DecAttnArgs dec_attn_self(const GreedyWS& g, int l, int B, int max_len, int host_step1);
 DecAttnArgs dec_attn_cross(const GreedyWS& g, int l, int B, int S, const uint8_t* src_mask);

@@ -237,6 +237,9 @@ hipError_t launch_pack_ffn(const int8_t* W1, const int8_t* W2, int F, int8_t* ou
 hipError_t launch_gemm(const GemmArgs& a, int wbits, hipStream_t st);
 hipError_t launch_skinny(const SkinnyArgs& a, int wbits, hipStream_t st);
 hipError_t launch_dec_attn(const DecAttnArgs& a, int B, hipStream_t st);
+// its kernel for 129 .. 512 rows to load (four waves per (sentence, head); a validated by
+// launch_dec_attn, which dispatches here)
+hipError_t launch_dec_attn_long(const DecAttnArgs& a, int B, hipStream_t st);
 // [B * S, 512] int8 values (L layers, layer stride v_ls) -> k_dec_attn's 4-key group layout
 // (DecAttnArgs::vc; layer stride o_ls, B * ceil(S / 4) * 2048 bytes per layer)
 hipError_t launch_vgroup4(const int8_t* v, long v_ls, int L, int B, int S, int8_t* out,

@@ -227,8 +227,8 @@ int32_t qtx_decode_attention(int32_t kv_new, const float* y, int64_t ldy, int8_t
                              int32_t B, float* ctx, float* pmax, void* stream) {
   if (!y || !kc || !vc || !skc || !svc || !ctx || !pmax)
     return fail(QTX_E_INVALID, "null argument");
-  if (kv_new ? (!step_dev || kv_bs <= 0 || kv_bs > 128)
-             : (!mask || S <= 0 || S > 128 || S > kv_bs))
+  if (kv_new ? (!step_dev || kv_bs <= 0 || kv_bs > 512)
+             : (!mask || S <= 0 || S > 512 || S > kv_bs))
     return fail(QTX_E_INVALID, "decode attention: bad step/mask/S/kv_bs");
   // y rows and the cached key / value rows are read in 16-byte vectors
   if (!aligned16(y) || !aligned16(kc) || !aligned16(vc) || ldy % 4 || ldy < (kv_new ? 1536 : 512))
