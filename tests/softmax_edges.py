@@ -33,9 +33,23 @@ moves the context by |v| * s_v / 127 and nothing cancels it.  The case builders 
 what one GPU case feeds to a kernel together with the oracle's view of it; the CPU test checks
 the construction and counts, per case, the query rows whose OUTPUT each wrong model changes.
 
-Generation is deterministic and cached.  Measured on the CPU: both pools 1.2 s, the 18 cases
-0.8 s, the oracle's expectations of all of them 3.6 s; tests/test_softmax_edges_ref.py as a
-whole 12 s."""
+Past 128 keys (k_dec_attn_long: four waves, wave w scoring the keys [128 w, 128 w + 128)) the
+pair of a decode case visits the edges of every wave's block and lies in two different blocks
+in half to two thirds of the sentences; cross254x / cross512x hold the exact ties there (a fully
+masked sentence, 254 and 512 equal live keys, two equal keys in different waves).
+
+A two-key row cannot tell in which ORDER the denominator is summed.  The *_order cases
+(order_case) add dust keys to the pair and keep, per dust layout and tie, the floats at which
+a wrong order (ORDER_MODELS: per-wave sums, key order, float64) gives key B another code than
+the oracle's lane-split order; the builder adds layouts until every model has 16 such rows, the
+fewest layouts that do (3, 7, 3 and 2 for the four cases).
+
+Generation is deterministic and cached.  Measured on the CPU: both pools 1.2 s, the first 18
+cases 0.8 s, the oracle's expectations of all of them 3.6 s.  The 8 pair cases past 128 keys
+hold 288 sentences of up to 512 keys each (the fewest rows select() can give with every tie
+on both sides) and take 1 - 2.5 s each to build, 0.4 - 0.8 s for the oracle's expectation and
+about 1 s for the models' counts; the four order cases 2.1 s for all their layouts.
+tests/test_softmax_edges_ref.py as a whole: 45 s where the first 18 cases alone took 12 s."""
 import functools
 
 import numpy as np
@@ -77,10 +91,39 @@ def exps(scores):
     return O.qexp(scores - scores.max(axis=-1)[..., None])
 
 
+def sum_wave_sums(e):
+    """The denominator a four-wave kernel gets from per-wave sums: a lane-split sum over each
+    key block [128 w, 128 w + 128), added (s0 + s1) + (s2 + s3).  Up to 128 keys it IS the
+    canonical order."""
+    e = np.asarray(e, f32)
+    assert e.shape[-1] <= 512
+    s = [O.row_sum_lanesplit(e[..., 128 * w:128 * w + 128]) if e.shape[-1] > 128 * w
+         else np.zeros(e.shape[:-1], f32) for w in range(4)]
+    return ((s[0] + s[1]) + (s[2] + s[3])).astype(f32)
+
+
+def sum_sequential(e):
+    """The keys added one after the other in key order."""
+    return np.add.accumulate(np.asarray(e, f32), axis=-1, dtype=f32)[..., -1]
+
+
+def sum_f64(e):
+    """Summed in float64 and rounded once."""
+    return np.asarray(e, np.float64).sum(-1).astype(f32)
+
+
+# wrong orders of the denominator's sum: everything else as the oracle
+ORDER_TOTALS = {"wave_sums": sum_wave_sums, "sequential": sum_sequential, "f64": sum_f64}
+ORDER_MODELS = tuple(ORDER_TOTALS)
+
+
 def codes_from(e, model=None, total=O.row_sum_lanesplit):
     """rint(p * 127) from the exponentials e [..., Sk] as the oracle (model None) or as a wrong
-    model computes it.  total: the denominator's sum over the last axis."""
+    model computes it.  total: the denominator's sum over the last axis (an ORDER_MODELS name
+    as the model selects its own)."""
     e = np.asarray(e, f32)
+    if model in ORDER_TOTALS:
+        total, model = ORDER_TOTALS[model], None
     if model in ("exp+", "exp-"):     # every computed exponential (not the 0s and the exact 1s)
         e = np.where((e > 0) & (e < 1), np.nextafter(e, _UP if model == "exp+" else _DN), e)
     den = np.asarray(total(e), f32)
@@ -263,7 +306,8 @@ def _signs(rng):
 
 def _nonzero(rng, shape):
     v = rng.integers(-127, 127, shape, dtype=np.int8)          # -127 .. 126 -> -127 .. -1, 1 .. 127
-    return (v + (v >= 0)).astype(np.int8)
+    v += v >= 0
+    return v
 
 
 def _rows(kind, idx, n_guard=0):
@@ -383,12 +427,35 @@ def _dec_slots(S):
     """Key positions a decode case moves its pair over: a lane's first and second slot, the
     fragment borders, the last keys before S and the first key of the last 16-group."""
     c = {0, 1, 5, 15, 16, 31, 47, 48, 63, 64, 65, 69, 100, 127, S - 1, S - 2, 16 * ((S - 1) // 16)}
+    if S > 128:     # k_dec_attn_long: the same in every wave's 128-key block
+        c = {S - 1, S - 2, 16 * ((S - 1) // 16)}
+        for w in range((S + 127) // 128):
+            c |= {128 * w + j for j in (0, 15, 16, 63, 64, 127)}
     return np.array(sorted(j for j in c if 0 <= j < S))
 
 
-def _dec_pair(B, S):
+def _dec_pair(B, S, fixed_a=None):
+    """(key A, key B) of B sentences over _dec_slots(S).  fixed_a (S > 128 only): key A where
+    it is >= 0 (a key outside the slots: the new key of a self-attention step).  Past 128 keys
+    two sentences of three (by the index of the sentence among those that choose the same way)
+    take key B from another wave's block than key A's and the third from the same one."""
     c = _dec_slots(S)
     b = np.arange(B)
+    if S > 128 or fixed_a is not None:
+        jA, jB = np.empty(B, np.int64), np.empty(B, np.int64)
+        seen = {}
+        for s in range(B):
+            fix = fixed_a is not None and fixed_a[s] >= 0
+            i = seen[fix] = seen.get(fix, -1) + 1
+            a = int(fixed_a[s]) if fix else int(c[i % len(c)])
+            far = c[(c >> 7) != (a >> 7)]
+            near = c[((c >> 7) == (a >> 7)) & (c != a)]
+            # (where a new key is fixed, the sentences that choose freely take the same wave
+            # twice in three: a new key alone in its block has no key B there)
+            same = (i + i // len(c)) % 3 == 2 if fix or fixed_a is None else (i + i // len(c)) % 3 != 0
+            cand = near if (same and len(near)) or not len(far) else far
+            jA[s], jB[s] = a, cand[(i // 3 + 5 * (i // len(c))) % len(cand)]
+        return jA, jB
     if len(c) == 1:
         return c[b * 0], c[b * 0]
     return c[b % len(c)], c[(b + 1 + (b // len(c)) % (len(c) - 1)) % len(c)]
@@ -439,6 +506,8 @@ def self_case(idx, step, seed, kv_bs=128):
     jA = np.where(new_a, step, pa)
     jB = np.where(new_a, pb if step > 1 else 0, pb)
     jB = np.where(jB == jA, pa, jB)
+    if step >= 128:       # k_dec_attn_long: key B's wave chosen against key A's
+        jA, jB = _dec_pair(B, step, np.where(new_a, step, -1))
     assert np.all(jA != jB) and np.all(jB < step)
     kc = rng.integers(-127, 128, (B, kv_bs, 512), dtype=np.int8)
     skc = rng.uniform(0.002, 0.03, (B, kv_bs)).astype(f32)
@@ -450,28 +519,203 @@ def self_case(idx, step, seed, kv_bs=128):
     svc = rng.uniform(0.002, 0.03, (B, kv_bs)).astype(f32)
     svc[:, step] = SV_NEW
     vc[b, step, rng.integers(0, 512, B)] = np.where(vc[b, step, 0] == 0, 0, 127)
+    out = _self_pack(rng, sgn, kc, skc, vc, svc, step, kv_bs)
+    out["intended"]["new_a"] = _ro(new_a)
+    return dict(out, jA=_ro(jA[:, None]), jB=_ro(jB[:, None]), obs=_ro(obs[:, None]),
+                src=_ro(src[:, None]), pairs=True)
+
+
+def _self_pack(rng, sgn, kc, skc, vc, svc, step, kv_bs):
+    """The y rows, the caches before (stale codes and scales at row `step`) and after the step
+    and the oracle's view of a self-attention case whose intended caches are kc .. svc."""
+    B, n = len(kc), step + 1
     y = np.empty((B, 1536), f32)
     y[:, :512] = sgn * (f32(127.0) * SQ_DEC)
     y[:, 512:1024] = kc[:, step].astype(f32) * skc[:, step, None]   # exact: +-127 * 2^e
     y[:, 1024:] = vc[:, step].astype(f32) * SV_NEW
     stale = rng.integers(-127, 128, (B, 512)).astype(np.int8)
+    intended = dict(kc=_ro(kc[:, step].astype(np.int8)), skc=_ro(skc[:, step].copy()),
+                    vc=_ro(vc[:, step].copy()))
+    # (kc and vc, the caller's own arrays, become the caches after the step: of the large
+    # arrays only the caches before it are copies)
     raw = dict(y=y, kc=kc.astype(np.int8), vc=vc.copy(), skc=skc.copy(), svc=svc.copy())
     raw["kc"][:, step], raw["vc"][:, step] = stale, stale[:, ::-1]     # what the step overwrites
     raw["skc"][:, step] = raw["svc"][:, step] = f32(0.5)
     qq, sq = O.quant_rows(y[:, :512])
     qk, sk = O.quant_rows(y[:, 512:1024])
     qv, sv = O.quant_rows(y[:, 1024:])
-    after = dict(kc=raw["kc"].copy(), vc=raw["vc"].copy(), skc=raw["skc"].copy(), svc=raw["svc"].copy())
+    after = dict(kc=kc if kc.dtype == np.int8 else kc.astype(np.int8), vc=vc, skc=skc, svc=svc)
     after["kc"][:, step], after["vc"][:, step] = qk, qv
     after["skc"][:, step], after["svc"][:, step] = sk, sv
     view = dict(q=qq[:, None], sq=sq[:, None], k=after["kc"][:, :n], sk=after["skc"][:, :n],
                 v=after["vc"][:, :n], sv=after["svc"][:, :n], mask=np.ones((B, 1, n), np.uint8))
     return dict(view={a: _ro(c) for a, c in view.items()}, raw={a: _ro(c) for a, c in raw.items()},
                 after={a: _ro(c) for a, c in after.items()}, step=step, kv_bs=kv_bs,
-                intended=dict(kc=_ro(kc[:, step].astype(np.int8)), skc=_ro(skc[:, step]),
-                              vc=_ro(vc[:, step]), new_a=_ro(new_a)),
-                jA=_ro(jA[:, None]), jB=_ro(jB[:, None]), obs=_ro(obs[:, None]),
-                src=_ro(src[:, None]), kind="dec", pairs=True, by_obs=True, dec=True)
+                intended=intended, kind="dec", by_obs=True, dec=True)
+
+
+def _view_exps(v):
+    """e [B, 8, Sq, Sk] of the oracle's view of a case, 32 sentences at a time."""
+    return np.concatenate([
+        exps(O.attention_scores(O.split_heads(v["q"][s], 8), v["sq"][s], O.split_heads(v["k"][s], 8),
+                                v["sk"][s], v["mask"][s]))
+        for s in (slice(lo, lo + 32) for lo in range(0, len(v["q"]), 32))])
+
+
+def _cross_pack(y, kc, vc, skc, svc, mask):
+    """What a cross-attention case feeds to the kernel (raw) and the oracle's view of it."""
+    raw = dict(y=y, kc=kc.astype(np.int8), vc=vc.astype(np.int8), skc=skc.astype(f32),
+               svc=svc.astype(f32), mask=mask.astype(np.uint8))
+    qq, sq = O.quant_rows(y)
+    view = dict(q=qq[:, None], sq=sq[:, None], k=raw["kc"], sk=raw["skc"], v=raw["vc"],
+                sv=raw["svc"], mask=raw["mask"][:, None])
+    return dict(view={n: _ro(a) for n, a in view.items()}, raw={n: _ro(a) for n, a in raw.items()},
+                kind="dec", by_obs=True, dec=True)
+
+
+def exact_dec_case(S, kinds, seed):
+    """The exact ties at qtx_decode_attention (kv_new = 0), every key with key A's pattern and
+    scale, one sentence per entry of kinds: "masked" (no key kept: uniform over S), "all" (S
+    live equal keys) or "two" (two live equal keys, in different waves' blocks)."""
+    rng = np.random.default_rng(SEED + seed)
+    B = len(kinds)
+    sgn = np.stack([_signs(rng) for _ in range(B)])
+    y = (sgn * (f32(127.0) * SQ_DEC)).astype(f32)
+    kc = np.repeat((sgn * 127)[:, None, :], S, 1)
+    mask = np.zeros((B, S), np.uint8)
+    n = np.full((B, 1), S, np.int64)
+    for b, kind in enumerate(kinds):
+        if kind == "all":
+            mask[b] = 1
+        elif kind == "two":
+            mask[b, [(29 * b + 3) % 128, 128 + (71 * b + 5) % (S - 128)]] = 1
+            n[b] = 2
+    c = _cross_pack(y, kc, _nonzero(rng, (B, S, 512)), np.full((B, S), SKA_DEC, f32),
+                    rng.uniform(0.002, 0.03, (B, S)), mask)
+    return dict(c, n=_ro(n), pairs=False)
+
+
+# ------------------------------------------------------------------ the denominator's order
+# A two-key row has den = 1 + e_B, which has no order.  An order row has key A (e == 1), key B
+# (swept, observed) and "dust": keys 2 .. 7 below key A, each with its own scale, spread over
+# lanes and waves.  Key A is the pairs' (SKA_DEC: a score of 2^-7, so x = fl(score - score_A)
+# keeps the grid of its own ulp and a sweep of a scale visits every float x); key B and the dust
+# carry the opposite sign pattern, the dust as one integer magnitude per key on all 64 dims of
+# all heads, so every head scores alike.  The dust moves the denominator's low bits differently
+# in every order of summation; a code of key B feels one ulp of the denominator only where x's
+# grid is finer than that, which is at the higher ties (|x| < 1).
+ORDER_WINDOW = 256                    # (one ulp of the denominator moves a flip by a few floats)
+ORDER_KEEP = 2                        # rows kept per (layout, tie, order model)
+ORDER_MAX_LAYOUTS = 24
+
+
+def _ord_score(acc, sk):
+    """The oracle's score of an accumulator: ((acc * s_q) * s_k) / 8 with s_q = SQ_DEC."""
+    return ((np.asarray(acc, f32) * SQ_DEC) * np.asarray(sk, f32)) / f32(8.0)
+
+
+@functools.lru_cache(maxsize=None)
+def order_layout(S, n_dust, ties, models, seed, a_fixed=-1):
+    """One dust layout of S keys (a_fixed >= 0: key A's position, the others among the keys
+    below it) and its kept rows: for every tie in `ties` on key B's code the floats t (key B's
+    scale) within ORDER_WINDOW of the oracle's flip at which some model of `models` gives key B
+    another code than the oracle, ORDER_KEEP per model, nearest first.  Read-only arrays: jA,
+    jB, pos / mag / sd [n_dust] (the dust keys, their code magnitudes and scales) and t, tie,
+    code_b [n], bad [n, len(models)]."""
+    rng = np.random.default_rng(SEED + 7919 * seed + 31 * S + n_dust)
+    n_keys = S if a_fixed < 0 else a_fixed
+    pa, pb = _dec_pair(seed + 1, n_keys, None if a_fixed < 0 else np.full(seed + 1, a_fixed))
+    jA, jB = int(pa[seed]), int(pb[seed])
+    free = np.setdiff1d(np.arange(n_keys), [jA, jB])
+    pos = np.sort(rng.choice(free, n_dust, replace=False))
+    mag = rng.integers(64, 128, n_dust)
+    s_a = _ord_score(ACC, SKA_DEC)
+    sd = (-(float(s_a) + rng.uniform(-7.0, -2.0, n_dust)) * 8.0
+          / (64.0 * 127.0 * mag * float(SQ_DEC))).astype(f32)
+    e0 = np.zeros(S, f32)
+    e0[jA] = 1
+    e0[pos] = O.qexp(_ord_score(-64 * 127 * mag, sd) - s_a)
+
+    def codes(t, model=None):
+        e = np.repeat(e0[None], len(t), 0)
+        e[:, jB] = O.qexp(_ord_score(-ACC, t) - s_a)
+        return codes_from(e, model)[:, jB].astype(int)
+
+    rec = []
+    lo, hi = _bits(1e-12), _bits(1.0)
+    for tie in ties:
+        pred = lambda t: bool(codes(np.atleast_1d(t))[0] <= tie)
+        if pred(_floats(lo)):                             # the dust keeps key B below this code
+            break
+        flip = _bisect(pred, lo, hi)
+        bits = np.arange(flip - ORDER_WINDOW, min(flip + ORDER_WINDOW, hi + 1), dtype=np.int64)
+        ref = codes(_floats(bits))
+        bad = np.stack([codes(_floats(bits), m) != ref for m in models], -1)
+        order = np.argsort(np.abs(bits - flip + 0.5), kind="stable")
+        keep = set()
+        for m in range(len(models)):
+            keep.update(int(i) for i in order[bad[order, m]][:ORDER_KEEP])
+        rec += [(bits[i], tie, ref[i]) + tuple(bad[i]) for i in sorted(keep)]
+    a = np.array(rec, np.int64).reshape(-1, 3 + len(models))
+    out = dict(jA=jA, jB=jB, pos=pos, mag=mag, sd=sd, t=_floats(a[:, 0]), tie=a[:, 1],
+               code_b=a[:, 2], bad=a[:, 3:].astype(bool))
+    return {k: _ro(v) if isinstance(v, np.ndarray) else v for k, v in out.items()}
+
+
+def order_case(entry, S, n_dust, ties, models, seed, min_rows=16, kv_bs=None):
+    """The kept rows of as many dust layouts as it takes for every model of `models` to get
+    min_rows rows wrong, one sentence per row.  entry "cross": qtx_decode_attention with
+    kv_new = 0 at S keys, everything but key A, key B and the dust masked.  entry "self":
+    kv_new = 1 at step S - 1, no mask, the other keys dead (SK_DEAD); in the even layouts the
+    new key is key A, in the odd ones a dead key."""
+    rng = np.random.default_rng(SEED + seed)
+    lays, got = [], np.zeros(len(models), int)
+    while (got < min_rows).any() or (entry == "self" and len(lays) < 2):
+        assert len(lays) < ORDER_MAX_LAYOUTS, (entry, S, dict(zip(models, got)))
+        a_fixed = S - 1 if entry == "self" and len(lays) % 2 == 0 else -1
+        lay = order_layout(S if entry == "cross" or a_fixed >= 0 else S - 1, n_dust, tuple(ties),
+                           tuple(models), 100 * seed + len(lays), a_fixed)
+        lays.append(lay)
+        got += lay["bad"].sum(0)
+    lay_of = np.concatenate([np.full(len(l["t"]), i) for i, l in enumerate(lays)])
+    B = len(lay_of)
+    b = np.arange(B)
+    sgn = np.stack([_signs(rng) for _ in range(B)])
+    jA = np.array([lays[i]["jA"] for i in lay_of])
+    jB = np.array([lays[i]["jB"] for i in lay_of])
+    rows = kv_bs or S
+    kc = rng.integers(-127, 128, (B, rows, 512), dtype=np.int8)
+    skc = rng.uniform(0.002, 0.03, (B, rows)).astype(f32)
+    vc = _nonzero(rng, (B, rows, 512))
+    svc = rng.uniform(0.002, 0.03, (B, rows)).astype(f32)
+    mask = np.zeros((B, S), np.uint8)
+    if entry == "self":
+        kc[:, :S], skc[:, :S] = (-sgn * 127)[:, None, :], SK_DEAD
+    for i, l in enumerate(lays):
+        r = np.flatnonzero(lay_of == i)[:, None]
+        kc[r, l["pos"]] = -sgn[r[:, 0], None, :] * l["mag"][None, :, None]
+        skc[r, l["pos"]], vc[r, l["pos"]], mask[r, l["pos"]] = l["sd"], 0, 1
+    kc[b, jA], skc[b, jA], vc[b, jA] = sgn * 127, SKA_DEC, 0
+    kc[b, jB], skc[b, jB] = -sgn * 127, np.concatenate([l["t"] for l in lays])
+    mask[b, jA] = mask[b, jB] = 1
+    info = dict(jA=_ro(jA[:, None]), jB=_ro(jB[:, None]), obs=_ro(np.zeros((B, 1), np.int64)),
+                layout=_ro(lay_of), n_layouts=len(lays), pairs=False, order_models=tuple(models),
+                tie=_ro(np.concatenate([l["tie"] for l in lays])),
+                code_b=_ro(np.concatenate([l["code_b"] for l in lays])),
+                bad=_ro(np.concatenate([l["bad"] for l in lays])))
+    if entry == "cross":
+        y = (sgn * (f32(127.0) * SQ_DEC)).astype(f32)
+        c = dict(_cross_pack(y, kc, vc, skc, svc, mask), **info)
+    else:
+        step = S - 1
+        svc[:, step] = SV_NEW
+        vc[b, step, rng.integers(0, 512, B)] = np.where(vc[b, step, 0] == 0, 0, 127)
+        c = dict(_self_pack(rng, sgn, kc, skc, vc, svc, step, rows), **info)
+    # the oracle's own codes on these rows are the ones the sweep recorded, in every head
+    e = _view_exps(c["view"])[:, :, 0]
+    assert np.all(e[b, :, jA] == 1) and np.all((e > 0).sum(-1) == n_dust + 2)
+    assert np.all(codes_from(e)[b, :, jB] == info["code_b"][:, None]), (entry, S)
+    return c
 
 
 # ------------------------------------------------------------------ the cases
@@ -501,7 +745,26 @@ CASES = {
     "self63": ("self", lambda: self_case(select("dec", 280, 6), 63, 14)),
     "self64": ("self", lambda: self_case(select("dec", 280, 7), 64, 15)),
     "self127": ("self", lambda: self_case(select("dec", 280, 8), 127, 16)),
+    # k_dec_attn_long (129 to 512 rows to load)
+    "cross129": ("cross", lambda: cross_case(select("dec", 280, 9), 129, 17)),
+    "cross257": ("cross", lambda: cross_case(select("dec", 280, 10), 257, 18)),
+    "cross511": ("cross", lambda: cross_case(select("dec", 280, 11), 511, 19)),
+    "cross512": ("cross", lambda: cross_case(select("dec", 280, 12), 512, 20)),
+    "self128": ("self", lambda: self_case(select("dec", 280, 13), 128, 21, kv_bs=512)),
+    "self255": ("self", lambda: self_case(select("dec", 280, 14), 255, 22, kv_bs=512)),
+    "self256": ("self", lambda: self_case(select("dec", 280, 15), 256, 23, kv_bs=512)),
+    "self511": ("self", lambda: self_case(select("dec", 280, 16), 511, 24, kv_bs=512)),
+    "cross254x": ("cross", lambda: exact_dec_case(254, ("masked", "all", "two") * 2, 25)),
+    "cross512x": ("cross", lambda: exact_dec_case(512, ("all", "masked", "two"), 26)),
+    "cross512_order": ("cross", lambda: order_case("cross", 512, 40, range(1, 62, 3), ORDER_MODELS, 27)),
+    "cross257_order": ("cross", lambda: order_case("cross", 257, 100, range(1, 62, 3), ORDER_MODELS, 28)),
+    "self511_order": ("self", lambda: order_case("self", 512, 40, range(1, 62, 3), ORDER_MODELS, 29)),
+    # k_dec_attn at two lane rounds (per-wave sums are the canonical order there)
+    "cross128_order": ("cross", lambda: order_case("cross", 128, 60, range(1, 62, 3), ORDER_MODELS[1:], 30)),
 }
+EXACT_DEC = ("cross254x", "cross512x")
+ORDER = ("cross512_order", "cross257_order", "self511_order", "cross128_order")
+OLD_18 = tuple(CASES)[:18]            # the cases of k_attn_*, k_attention and k_dec_attn's pairs
 
 
 def names(entry):
@@ -518,9 +781,10 @@ def expected(name, dec=False):
     """The oracle's (context [B, Sq, 512], codes [B, 8, Sq, Sk]) of a case."""
     c = case(name)
     v = c["view"]
-    ctx, qp = O.attention(v["q"], v["sq"], v["k"], v["sk"], v["v"], v["sv"], v["mask"], 8,
-                          dec=bool(c.get("dec", dec)))
-    return _ro(ctx), _ro(qp)
+    # (sentences are independent: 32 at a time keeps the oracle's int64 operands in the cache)
+    out = [O.attention(*(v[n][lo:lo + 32] for n in ("q", "sq", "k", "sk", "v", "sv", "mask")), 8,
+                       dec=bool(c.get("dec", dec))) for lo in range(0, len(v["q"]), 32)]
+    return _ro(np.concatenate([o[0] for o in out])), _ro(np.concatenate([o[1] for o in out]))
 
 
 def expected_quant(name):
@@ -532,9 +796,28 @@ def expected_quant(name):
 @functools.lru_cache(maxsize=None)
 def case_exps(name):
     """e [B, 8, Sq, Sk] of a case (what every model starts from)."""
-    v = case(name)["view"]
-    return _ro(exps(O.attention_scores(O.split_heads(v["q"], 8), v["sq"], O.split_heads(v["k"], 8),
-                                       v["sk"], v["mask"])))
+    return _ro(_view_exps(case(name)["view"]))
+
+
+def _pv_live(codes, v4, sv, dec):
+    """O.attention_pv of one-query rows (codes [n, 8, Sk], v4 [n, 8, Sk, 64], sv [n, Sk]) over
+    the keys alone to which some row gives a nonzero code.  A key with P == 0 leaves its chain as
+    it is (fma(0, v, acc) == acc for finite v), so this is the oracle's result bit for bit at a
+    fraction of 512 chain steps.  dec: the kept keys stay in their chains ((j >> 2) & 3) and
+    in key order: the i-th kept key of chain c goes to position 16 (i / 4) + 4 c + i % 4."""
+    keep = np.flatnonzero((codes != 0).any(axis=(0, 1)))
+    pos = np.arange(len(keep))
+    if dec:
+        for c in range(4):
+            mine = ((keep >> 2) & 3) == c
+            i = np.arange(mine.sum())
+            pos[mine] = 16 * (i // 4) + 4 * c + i % 4
+    n2 = int(pos.max()) + 1 if len(keep) else 1
+    c2 = np.zeros(codes.shape[:2] + (1, n2), codes.dtype)
+    v2 = np.zeros(v4.shape[:2] + (n2, v4.shape[3]), v4.dtype)
+    s2 = np.ones((len(sv), n2), f32)
+    c2[:, :, 0, pos], v2[:, :, pos], s2[:, pos] = codes[:, :, keep], v4[:, :, keep], sv[:, keep]
+    return O.attention_pv(c2, v2, s2, dec)
 
 
 @functools.lru_cache(maxsize=None)
@@ -559,7 +842,7 @@ def changed_all(name, dec, output, models):
     v4 = O.split_heads(v["v"], 8)
     for lo in range(0, len(where), 160):
         m, b, i = where[lo:lo + 160].T
-        got = O.merge_heads(O.attention_pv(alt[m, b, :, i][:, :, None, :], v4[b], v["sv"][b], dec))[:, 0]
+        got = O.merge_heads(_pv_live(alt[m, b, :, i], v4[b], v["sv"][b], dec))[:, 0]
         if output == "quant":
             (qa, sa), (qb, sb) = O.quant_rows(got), O.quant_rows(ctx[b, i])
             res[lo:lo + 160] = (qa != qb).any(-1) | (sa != sb)
@@ -571,9 +854,9 @@ def changed_all(name, dec, output, models):
 
 
 def changed_rows(name, model, dec=False, output="ctx"):
-    """bool [B, Sq] of one model (changed_all over MODELS, or over EXACT_MODELS)."""
+    """bool [B, Sq] of one model (changed_all over MODELS, EXACT_MODELS or ORDER_MODELS)."""
     dec = bool(case(name).get("dec", dec))
-    group = MODELS if model in MODELS else EXACT_MODELS
+    group = MODELS if model in MODELS else EXACT_MODELS if model in EXACT_MODELS else ORDER_MODELS
     return changed_all(name, dec, output, group)[model]
 
 

@@ -930,6 +930,89 @@ def test_decode_cross_attention(gb, masked_sentence):
     np.testing.assert_array_equal(np_(svd), svp)
 
 
+def test_decode_self_attention_long(gb):
+    """k_dec_attn_long: step 200 in kv_bs = 262 (66 value groups, the last one half pad keys),
+    B = 3, y at ldy = 1536 + 8 with NaN gaps; row `step` changes alone, the grouped-V pad keys
+    included, and everything lies between guard bands."""
+    B, kv_bs, step = 3, 262, 200
+
+    def ref():
+        rng = np.random.default_rng(B * 1000 + step)
+        y = rng.standard_normal((B, 1536)).astype(f32)
+        kc = rng.integers(-127, 128, (B, kv_bs, 512)).astype(np.int8)
+        vc = rng.integers(-127, 128, (B, kv_bs, 512)).astype(np.int8)
+        skc = rng.uniform(0.002, 0.03, (B, kv_bs)).astype(f32)
+        svc = rng.uniform(0.002, 0.03, (B, kv_bs)).astype(f32)
+        qq, sq = O.quant_rows(y[:, :512])
+        qk, sk = O.quant_rows(y[:, 512:1024])
+        qv, sv = O.quant_rows(y[:, 1024:])
+        kc2, vc2, skc2, svc2 = kc.copy(), vc.copy(), skc.copy(), svc.copy()
+        kc2[:, step], vc2[:, step], skc2[:, step], svc2[:, step] = qk, qv, sk, sv
+        n = step + 1
+        ctx, _ = O.attention(qq[:, None], sq[:, None], kc2[:, :n], skc2[:, :n], vc2[:, :n],
+                             svc2[:, :n], np.ones((B, 1, n), np.uint8), dec=True)
+        return y, (kc, vc, skc, svc), (kc2, vc2, skc2, svc2), ctx[:, 0]
+    y, (kc, vc, skc, svc), (kc2, vc2, skc2, svc2), ctx = memo(("dself_long", step), ref)
+    kcd, vcd = gb.init(kc, "kc"), gb.init(vgroup4(vc, 0x7f), "vc")
+    skd, svd = gb.init(skc, "skc"), gb.init(svc, "svc")
+    ctxd, pm = gb.new((B, 512), f32, "ctx"), gb.new((8, B), f32, "pmax")
+    call("qtx_decode_attention", 1, P(gb.pad(y, 1536 + 8, NAN)), 1536 + 8, P(kcd), P(vcd),
+         P(skd), P(svd), kv_bs, P(gb.dev(np.array([step], np.int32))), 0, S0, B, P(ctxd), P(pm),
+         S0)
+    gb.check()
+    np.testing.assert_array_equal(np_(kcd), kc2)
+    np.testing.assert_array_equal(np_(vcd), vgroup4(vc2, 0x7f))
+    np.testing.assert_array_equal(np_(skd), skc2)
+    np.testing.assert_array_equal(np_(svd), svc2)
+    np.testing.assert_array_equal(np_(ctxd), ctx)
+    np.testing.assert_array_equal(np_(pm), head_max(ctx))
+
+
+@pytest.mark.parametrize("masked_sentence", [False, True])
+def test_decode_cross_attention_long(gb, masked_sentence):
+    """k_dec_attn_long: S = 130 keys inside kv_bs = 138 cache rows (no multiple of 4: 35 value
+    groups per sentence, which the kernel derives from kv_bs), B = 3.  Rows 130 .. 137 hold 0x7f
+    codes and NaN scales, y lies at ldy = 512 + 8 with NaN gaps; none of them may reach the
+    result, and the caches are read only."""
+    B, S, kv_bs = 3, 130, 138
+
+    def ref():
+        rng = np.random.default_rng(B + S + masked_sentence)
+        y = rng.standard_normal((B, 512)).astype(f32)
+        kc = rng.integers(-127, 128, (B, S, 512)).astype(np.int8)
+        vc = rng.integers(-127, 128, (B, S, 512)).astype(np.int8)
+        skc = rng.uniform(0.002, 0.03, (B, S)).astype(f32)
+        svc = rng.uniform(0.002, 0.03, (B, S)).astype(f32)
+        mask = np.ones((B, S), np.uint8)
+        mask[0, 100:] = 0
+        mask[2, 1::3] = 0
+        if masked_sentence:
+            mask[1, :] = 0
+        qq, sq = O.quant_rows(y)
+        ctx, _ = O.attention(qq[:, None], sq[:, None], kc, skc, vc, svc, mask[:, None], dec=True)
+        return y, kc, vc, skc, svc, mask, ctx[:, 0]
+    y, kc, vc, skc, svc, mask, ctx = memo(("dcross_long", masked_sentence), ref)
+    kcp = np.full((B, kv_bs, 512), 0x7f, np.int8)
+    kcp[:, :S] = kc
+    vcp = np.full((B, kv_bs, 512), 0x7f, np.int8)
+    vcp[:, :S] = vc
+    skp, svp = np.full((B, kv_bs), NAN, f32), np.full((B, kv_bs), NAN, f32)
+    skp[:, :S], svp[:, :S] = skc, svc
+    assert vgroup4(vcp).shape == (B, 35, 512, 4)
+    kcd, vcd = gb.init(kcp, "kc"), gb.init(vgroup4(vcp), "vc")
+    skd, svd = gb.init(skp, "skc"), gb.init(svp, "svc")
+    ctxd, pm = gb.new((B, 512), f32, "ctx"), gb.new((8, B), f32, "pmax")
+    call("qtx_decode_attention", 0, P(gb.pad(y, 512 + 8, NAN)), 512 + 8, P(kcd), P(vcd), P(skd),
+         P(svd), kv_bs, S0, S, P(gb.dev(mask)), B, P(ctxd), P(pm), S0)
+    gb.check()
+    np.testing.assert_array_equal(np_(ctxd), ctx)
+    np.testing.assert_array_equal(np_(pm), head_max(ctx))
+    np.testing.assert_array_equal(np_(kcd), kcp)                 # read only
+    np.testing.assert_array_equal(np_(vcd), vgroup4(vcp))
+    np.testing.assert_array_equal(np_(skd), skp)
+    np.testing.assert_array_equal(np_(svd), svp)
+
+
 def test_decode_attention_misaligned_is_invalid(gb):
     """y is read in 16-byte vectors: ldy % 4 != 0, ldy below the row width or a base off
     16 bytes is QTX_E_INVALID on the host; nothing is launched."""

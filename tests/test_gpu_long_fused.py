@@ -4,7 +4,10 @@ and its graphs at max_len = 140 and S = 132 — against the oracle, bit for bit.
 
 The key counts are the kernel's edges: 129 (one key in the second wave's block and the third
 lane round), 257 (one key in the third wave's block), 511 / 512 (the ragged and the full last
-round); the self-attention steps put the new key first and last in a wave's block."""
+round); the self-attention steps put the new key first and last in a wave's block.  Random
+caches give most keys P == 0, so test_cross_one_hot and test_self_every_step put P == 127 on
+one key slot after the other and on every step's patch of the new key, value byte and scales."""
+import ctypes as C
 import os
 import sys
 
@@ -14,6 +17,7 @@ import pytest
 from oracle import qtx_oracle as O
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import long_attn as LA  # noqa: E402
 import long_target as LT  # noqa: E402
 from guarded import guarded  # noqa: E402
 from test_gpu_fused import P, S0, _release, call, dev, head_max, torch, vgroup4  # noqa: E402,F401
@@ -94,6 +98,75 @@ def test_self_attention(torch, step, kv_bs):
     for got, want in ((kcd, kc), (vcd, vgroup4(vc)), (skd, skc), (svd, svc), (ctxd, ctx[:, 0]),
                       (pm, head_max(ctx[:, 0]))):
         np.testing.assert_array_equal(got.cpu().numpy(), want)
+
+
+# ---- every key slot and every step, directed (tests/long_attn.py) ----------------------------
+@pytest.mark.parametrize("S", [129, 511, 512])
+def test_cross_one_hot(torch, S):
+    """B = S sentences in one launch, sentence b keeps key b alone: P == 127 / 127 on one key
+    slot after the other, random nonzero values and scales everywhere.  The context is that
+    key's value row times its scale, so a wrong value byte, group dword, clamp or scale of any
+    one slot fails its sentence."""
+    c = LA.one_hot(S)
+    qq, sq = O.quant_rows(c["y"])
+    ctx, qp = LA.attention_chunked(qq, sq, c["kc"], c["skc"], c["vc"], c["svc"], c["mask"])
+    np.testing.assert_array_equal(qp, np.repeat((127 * np.eye(S, dtype=np.int8))[:, None], 8, 1))
+    np.testing.assert_array_equal(ctx, c["ctx"])        # RN(RN(1 * s_v[b, b]) * v[b, b, :])
+    ctxd, c0 = guarded(torch, (S, 512), torch.float32, 0x5A, name="ctx")
+    pm, c1 = guarded(torch, (8, S), torch.float32, 0x5A, name="pmax")
+    call("qtx_decode_attention", 0, P(dev(torch, c["y"])), 512, P(dev(torch, c["kc"])),
+         P(dev(torch, vgroup4(c["vc"]))), P(dev(torch, c["skc"])), P(dev(torch, c["svc"])), S, S0, S,
+         P(dev(torch, c["mask"])), S, P(ctxd), P(pm), S0)
+    torch.cuda.synchronize()
+    c0()
+    c1()
+    np.testing.assert_array_equal(ctxd.cpu().numpy(), ctx)
+    np.testing.assert_array_equal(pm.cpu().numpy(), head_max(ctx))
+
+
+def test_self_every_step(torch):
+    """The steps 0 .. 511 at kv_bs = 512 (the dispatch is by kv_bs, so the steps below 128 run
+    k_dec_attn_long too), the position from the device counter, on one pair of caches.
+    Sentence 0: the new key is the only live one; sentence 1: a cached key that walks the slots,
+    the new key dead.  Row `step` holds stale codes and scales before the call.  After every
+    step the context, the head maxima and the whole caches are compared (on the device: the
+    caches before the call with row `step` replaced by the closed form's), the guard bands once
+    at the end."""
+    es = LA.EveryStep()
+    n = LA.KV_BS
+    rng = np.random.default_rng(9001)
+    kc = np.repeat(es.dead[:, None], n, 1)                       # every cached key dead
+    vc = rng.integers(-127, 128, (2, n, 512)).astype(np.int8)
+    skc, svc = np.full((2, n), LA.SK_DEAD, f32), rng.uniform(0.002, 0.03, (2, n)).astype(f32)
+    bufs = [filled(torch, a, nm) for a, nm in ((kc, "kc"), (vgroup4(vc), "vc"), (skc, "skc"), (svc, "svc"))]
+    (kcd, vcd, skd, svd), checks = zip(*bufs)
+    ctxd, c0 = guarded(torch, (2, 512), torch.float32, 0x5A, name="ctx")
+    pm, c1 = guarded(torch, (8, 2), torch.float32, 0x5A, name="pmax")
+    yd, steps = dev(torch, es.y), dev(torch, np.arange(n, dtype=np.int32))
+    qk, qv, sk, sv = (dev(torch, a) for a in (es.qk, es.qv, es.sk, es.sv))
+    stale_v = dev(torch, es.stale_v)
+    ctx_want = dev(torch, es.ctx)
+    pm_want = dev(torch, np.stack([head_max(c) for c in es.ctx]))
+    bad = []
+    for step in range(n):
+        for b, r, k_row, k_scale in es.before(step):
+            kcd[b, r].copy_(torch.from_numpy(np.array(k_row)))
+            skd[b, r] = float(k_scale)
+        vcd[:, step >> 2, :, step & 3] = stale_v[step]
+        svd[:, step] = float(LA.SV_STALE)
+        want = [t.clone() for t in (kcd, vcd, skd, svd)]
+        want[0][:, step], want[1][:, step >> 2, :, step & 3] = qk[step], qv[step]
+        want[2][:, step], want[3][:, step] = sk[step], sv[step]
+        call("qtx_decode_attention", 1, P(yd[step]), 1536, P(kcd), P(vcd), P(skd), P(svd), n,
+             C.c_void_p(steps.data_ptr() + 4 * step), 0, S0, 2, P(ctxd), P(pm), S0)
+        ok = [torch.equal(g, w) for g, w in zip((kcd, vcd, skd, svd), want)]
+        ok += [torch.equal(ctxd, ctx_want[step]), torch.equal(pm, pm_want[step])]
+        if not all(ok):
+            bad.append((step, ok))
+    torch.cuda.synchronize()
+    for chk in checks + (c0, c1):
+        chk()
+    assert not bad, f"{len(bad)} steps differ (kc, vc, skc, svc, ctx, pmax): {bad[:8]}"
 
 
 # ---- model level: the fused-capable models of the long-target regime ------------------------

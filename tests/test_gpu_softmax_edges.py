@@ -2,15 +2,24 @@
 their floating-point neighbours (tests/softmax_edges.py), bit-exact against the oracle.
 
 Each kernel forms e / den with a shortcut of its own: k_attn_mfma by div_cr behind a wave-wide
-range vote with the true division as the other branch, k_attn_encq and k_dec_attn by an
-unguarded div_cr, k_attention and k_attn_trace by the true division.  The rows hold two live keys
+range vote with the true division as the other branch, k_attn_encq, k_dec_attn and
+k_dec_attn_long by an unguarded div_cr, k_attention and k_attn_trace by the true division.
+qtx_decode_attention runs k_dec_attn up to 128 rows to load (S, or kv_bs at kv_new = 1) and
+k_dec_attn_long from 129 to 512: the cases cross17 .. cross128, self1 .. self127 and
+cross128_order are the former's, cross129 .. cross512, self128 .. self511 (kv_bs = 512),
+cross254x, cross512x and the other *_order cases the latter's.  The rows hold two live keys
 whose probabilities sit on a tie k + 1/2 (every k = 0 .. 126, from both sides), the exact ties
 of 2 and of 254 equal keys, and guard rows with e_B on either side of 2^-60 and of the flush
 threshold; in "i8_guard" one query of every 16 (one wave of k_attn_mfma) is such a guard row,
-so the true-division branch sees ties too.  That these inputs fail a kernel whose quotient,
-exponential or denominator is off by an ulp, or that rounds half away from zero, is shown on the
-CPU by tests/test_softmax_edges_ref.py (its counts are the sensitivity of this file); no
-tolerance anywhere here.
+so the true-division branch sees ties too.  Past 128 keys the pair sits in different waves'
+blocks in most sentences, so the row maximum and both exponentials cross LDS.  The *_order
+cases add "dust" keys to the pair: there the denominator depends on the ORDER of its sum, and
+a failure of one of them with the two-key cases passing means the kernel sums in another order
+than the oracle's lane-split one (per wave, in key order, or in a wider format: each changes
+the context of at least 16 of their rows).  That these inputs fail a kernel whose quotient,
+exponential or denominator is off by an ulp, that rounds half away from zero or that sums the
+denominator in another order is shown on the CPU by tests/test_softmax_edges_ref.py (its counts
+are the sensitivity of this file); no tolerance anywhere here.
 
 k_attn_fault_rows is not covered: it is reachable only through the model-level fault entry
 points, where the scores cannot be steered; it divides with the plain true division.
@@ -117,8 +126,12 @@ def test_attention_i8_quant(torch, name):
 
 @pytest.mark.parametrize("name", E.names("cross"))
 def test_decode_cross_attention(torch, name):
-    """k_dec_attn<false>: one query per sentence; S = 17 (one partial fragment), 64, 65 (the
-    second key slot holds one key) and 128."""
+    """One query per sentence.  k_dec_attn<false>: S = 17 (one partial fragment), 64, 65 (the
+    second key slot holds one key) and 128; cross128_order: the denominator's order at two lane
+    rounds.  k_dec_attn_long<false>: S = 129 (one key in the second wave's block), 257, 511 and
+    512, the pair on the edges of every wave's block; cross254x / cross512x: the fully masked
+    sentence, 254 and 512 equal live keys (den == 512) and two equal keys in different waves;
+    cross512_order / cross257_order: the denominator's order across four waves."""
     c = E.case(name)
     r = c["raw"]
     B, S = r["mask"].shape
@@ -133,9 +146,11 @@ def test_decode_cross_attention(torch, name):
 
 @pytest.mark.parametrize("name", E.names("self"))
 def test_decode_self_attention(torch, name):
-    """k_dec_attn<true> at the steps 1, 63, 64 and 127: no mask, the dead keys 126 below the
-    maximum; the new key is key A in half of the sentences and a dead key in the others.  The
-    caches and the head maxima are compared too."""
+    """k_dec_attn<true> at the steps 1, 63, 64 and 127, k_dec_attn_long<true> (kv_bs = 512) at
+    128 (the new key is the first key of the second wave's block), 255, 256 and 511, and
+    self511_order (the denominator's order; the dust keys are cached rows): no mask, the dead
+    keys 126 below the maximum; the new key is key A in half of the sentences and a dead key in
+    the others.  The caches and the head maxima are compared too."""
     c = E.case(name)
     r, after, step, kv_bs = c["raw"], c["after"], c["step"], c["kv_bs"]
     B = len(r["y"])

@@ -2,7 +2,10 @@
 the construction holds, every tie k + 1/2 of the 1/127 grid is met from both sides, each wrong
 model of the quotient, the exponential and the denominator changes the OUTPUT of the entry point
 the rows are sent to (so tests/test_gpu_softmax_edges.py would fail a kernel that computes like
-it), and the oracle's results equal a restatement of the two-key row written out below."""
+it), and the oracle's results equal a restatement of the two-key row written out below.  Past
+128 keys: where the pair lies among k_dec_attn_long's four waves, the exact ties at 254 and 512
+keys, and the order cases, on which every wrong order of the denominator's sum changes the
+output of at least 16 rows."""
 import os
 import sys
 from fractions import Fraction
@@ -18,7 +21,8 @@ import softmax_edges as E  # noqa: E402
 f32 = np.float32
 ALL = list(E.CASES)
 EXACT = ("trace254", "i8_254x")
-PAIRS = [n for n in ALL if n not in EXACT]
+PAIRS = [n for n in ALL if n not in EXACT + E.EXACT_DEC + E.ORDER]
+LONG_PAIRS = [n for n in PAIRS if E.CASES[n][0] in ("cross", "self") and n not in E.OLD_18]
 OP_DEC = {"trace": (False, True), "i8": (False, True), "i8_quant": (False,), "cross": (True,),
           "self": (True,)}
 MIN_ROWS = 16
@@ -307,7 +311,7 @@ def test_partial_tile_and_small_slots():
         assert len({j for j in E.case("encq16")[key].reshape(-1)}) == 16
 
 
-@pytest.mark.parametrize("name", E.names("cross") + E.names("self"))
+@pytest.mark.parametrize("name", [n for n in PAIRS if E.CASES[n][0] in ("cross", "self")])
 def test_decode_slots(name):
     """k_dec_attn: a lane's first and second key slot, the last key and the last 16-group."""
     c = E.case(name)
@@ -336,3 +340,170 @@ def test_guard_rows_as_wave_neighbours():
                  for w in range(0, Sq, 16)]
         assert all(n >= 8 for s, n in waves if s)
         assert all(s for s, _ in waves) if every else 0 < sum(s for s, _ in waves) < len(waves)
+
+
+# ------------------------------------------------------------------ k_dec_attn_long: the pairs
+def test_short_pairs_are_what_they_were():
+    """Up to 128 keys _dec_slots / _dec_pair return what they returned before the long cases
+    existed (restated here), so the k_dec_attn cases and their expectations did not move."""
+    def slots(S):
+        c = {0, 1, 5, 15, 16, 31, 47, 48, 63, 64, 65, 69, 100, 127, S - 1, S - 2, 16 * ((S - 1) // 16)}
+        return np.array(sorted(j for j in c if 0 <= j < S))
+
+    def pair(B, S):
+        c, b = slots(S), np.arange(B)
+        if len(c) == 1:
+            return c[b * 0], c[b * 0]
+        return c[b % len(c)], c[(b + 1 + (b // len(c)) % (len(c) - 1)) % len(c)]
+
+    for S in range(1, 129):
+        np.testing.assert_array_equal(E._dec_slots(S), slots(S))
+        for B in (1, 17, 288, 512):
+            for got, want in zip(E._dec_pair(B, S), pair(B, S)):
+                np.testing.assert_array_equal(got, want)
+    for name in ("cross17", "cross64", "cross65", "cross128"):
+        c = E.case(name)
+        B, S = c["raw"]["mask"].shape
+        np.testing.assert_array_equal(c["jA"][:, 0], pair(B, S)[0])
+        np.testing.assert_array_equal(c["jB"][:, 0], pair(B, S)[1])
+    assert len(E.OLD_18) == 18 and E.OLD_18[-1] == "self127" and not set(E.OLD_18) & set(LONG_PAIRS)
+
+
+def _long_slots(S):
+    """What the pair of a long case must visit: in every wave's block the first and last key of
+    both lane slots and a fragment border, the last two keys and the last 16-group's first."""
+    c = {S - 1, S - 2, 16 * ((S - 1) // 16)}
+    for w in range((S + 127) // 128):
+        c |= {128 * w + j for j in (0, 63, 64, 127, 15, 16)}
+    return {j for j in c if j < S}
+
+
+@pytest.mark.parametrize("name", LONG_PAIRS)
+def test_long_pairs(name):
+    """The rows to load are past 128 (k_dec_attn_long serves the case); each of key A and key B
+    visits every slot of every wave's block; in at least a third of the sentences the two lie in
+    different waves' blocks (the maximum and both exponentials cross LDS), in at least a sixth
+    in the same one."""
+    c = E.case(name)
+    jA, jB = c["jA"][:, 0], c["jB"][:, 0]
+    if E.CASES[name][0] == "self":
+        n = c["step"] + 1
+        assert c["kv_bs"] == 512 and c["step"] >= 128
+        want_b = _long_slots(c["step"]) if c["step"] > 128 else set(E._dec_slots(128))
+        want_a = want_b | {c["step"]}                    # the cached slots and the new key
+        if name == "self128":
+            assert (jA[::2] == 128).all() and (jA[::2] >> 7 == 1).all()   # the second wave's first key
+    else:
+        n = c["raw"]["mask"].shape[1]
+        want_a = want_b = _long_slots(n)
+    assert 128 < n <= 512
+    assert set(jA) >= want_a, sorted(want_a - set(jA))
+    assert set(jB) >= want_b, sorted(want_b - set(jB))
+    far = (jA >> 7) != (jB >> 7)
+    print(name, "different waves %.3f, the same wave %.3f" % (far.mean(), 1 - far.mean()))
+    assert far.mean() >= 1 / 3 and (~far).mean() >= 1 / 6
+
+
+# ------------------------------------------------------------------ the exact ties, decode
+@pytest.mark.parametrize("name", E.EXACT_DEC)
+def test_exact_ties_decode(name):
+    """The rule of test_exact_ties at qtx_decode_attention: the fully masked sentence and the
+    one of S equal live keys have p = 1 / S on every key (S = 254: p * 127 == 0.5, code 0, context
+    0; half away or a quotient one ulp high gives 1 everywhere), two equal keys in different
+    waves' blocks 64 / 64.  S = 512: den == 512, the largest denominator the kernel can meet."""
+    c = E.case(name)
+    n = c["n"][:, 0]
+    S = c["raw"]["mask"].shape[1]
+    ctx, qp = E.expected(name, True)
+    e = E.case_exps(name)
+    assert set(np.unique(e)) == {0.0, 1.0}
+    np.testing.assert_array_equal(O.row_sum_lanesplit(e)[:, :, 0], np.repeat(n[:, None], 8, 1))
+    for b, nb in enumerate(n):
+        live = qp[b, :, 0][e[b, :, 0] == 1]
+        assert live.size == 8 * nb and np.all(live == (64 if nb == 2 else 0))
+        if nb == 2:
+            j = np.flatnonzero(c["raw"]["mask"][b])
+            assert j[0] >> 7 != j[1] >> 7
+        else:
+            assert not ctx[b].any()
+    assert (n == S).sum() >= 2 and (n == 2).any()
+    assert (c["raw"]["mask"].sum(-1) == 0).any() and (c["raw"]["mask"].sum(-1) == S).any()
+    for m in E.EXACT_MODELS:
+        ch = E.changed_rows(name, m, True, "ctx")[:, 0]
+        np.testing.assert_array_equal(ch, n == 254)
+        assert ch.sum() >= (4 if S == 254 else 0)
+
+
+# ------------------------------------------------------------------ the denominator's order
+def test_random_rows_are_blind_to_the_order():
+    """Why the order cases exist: on random rows the wrong orders move the denominator by an ulp
+    in a third to nine tenths of the rows and a code in next to none."""
+    rng = np.random.default_rng(5)
+    e = E.exps(rng.standard_normal((4000, 512)).astype(f32))
+    ref = E.codes_from(e)
+    for m, lo in (("wave_sums", 0.25), ("sequential", 0.7), ("f64", 0.2)):
+        den = E.ORDER_TOTALS[m](e) != O.row_sum_lanesplit(e)
+        rows = (E.codes_from(e, m) != ref).any(-1)
+        print(m, "denominators %.3f, rows with another code %d of %d" % (den.mean(), rows.sum(), len(e)))
+        assert den.mean() > lo and rows.sum() <= 2
+
+
+@pytest.mark.parametrize("name", E.ORDER)
+def test_order_cases(name):
+    """Every wrong order of the denominator's sum that applies to the case changes the OUTPUT of
+    at least MIN_ROWS of its rows, and exactly the rows whose code of key B the sweep saw it get
+    wrong; the oracle's codes are the sweep's; key B alone carries values."""
+    entry = E.CASES[name][0]
+    c = E.case(name)
+    v = c["view"]
+    models = c["order_models"]
+    assert models == (E.ORDER_MODELS[1:] if name == "cross128_order" else E.ORDER_MODELS)
+    B, S = v["k"].shape[:2]
+    b = np.arange(B)
+    jA, jB = c["jA"][:, 0], c["jB"][:, 0]
+    e = E.case_exps(name)[:, :, 0]                                # [B, 8, S]
+    ctx, qp = E.expected(name, True)
+    assert np.all(e[b, :, jA] == 1) and np.all(e[b, :, jB] < 1)
+    np.testing.assert_array_equal(qp[b, :, 0, jB], np.repeat(c["code_b"][:, None], 8, 1))
+    dust = (e[:, 0] > 0) & (e[:, 0] < 1)
+    dust[b, jB] = False
+    assert (dust.sum(-1) >= 40).all()
+    ed = e[:, 0][dust]
+    assert ed.min() > np.exp(-7.01) and ed.max() < np.exp(-1.99)
+    # the dust is spread over the lanes and over every wave's block that has 16 keys or more
+    for i in range(c["n_layouts"]):
+        j = np.flatnonzero(dust[np.flatnonzero(c["layout"] == i)[0]])
+        assert len(set(j % 64)) >= 25 and set(j >> 7) >= {w for w in range(4) if S >= 128 * w + 16}
+        sk = v["sk"][np.flatnonzero(c["layout"] == i)[0]][j]
+        assert len(set(sk)) == len(j)                             # a scale of its own
+    assert np.all(v["v"][b, jB] != 0) and np.all(v["sv"] > 0)
+    live = e[:, 0] > 0
+    live[b, jB] = False
+    assert not v["v"][live].any()
+    if entry == "self":
+        assert c["step"] == 511 and c["kv_bs"] == 512
+        new_a = jA == c["step"]
+        assert new_a.any() and (~new_a).any()
+        assert np.all(v["sk"][~live & (np.arange(S) != jB[:, None])] == E.SK_DEAD)
+    counts = {}
+    for k, m in enumerate(models):
+        ch = E.changed_rows(name, m, True, "ctx")[:, 0]
+        np.testing.assert_array_equal(ch, c["bad"][:, k])
+        counts[m] = int(ch.sum())
+    print(name, "rows", B, "layouts", c["n_layouts"], "ties", len(set(c["tie"])), counts)
+    assert all(n >= MIN_ROWS for n in counts.values()), counts
+    assert c["bad"].any(-1).all()                                 # no row without a purpose
+    if name == "cross128_order":      # two lane rounds in one wave: per-wave sums are the canon
+        assert not E.changed_rows(name, "wave_sums", True, "ctx").any()
+
+
+def test_order_rows_equal_the_patched_oracle():
+    """On the cheapest order case the same rows change when the whole oracle runs with
+    O.softmax_quant replaced by the wrong order."""
+    name = "cross128_order"
+    v = E.case(name)["view"]
+    ctx = E.expected(name, True)[0]
+    for m in E.ORDER_MODELS:
+        with E.patched(m):
+            got, _ = O.attention(v["q"], v["sq"], v["k"], v["sk"], v["v"], v["sv"], v["mask"], 8, dec=True)
+        np.testing.assert_array_equal((got != ctx).any(-1), E.changed_rows(name, m, True, "ctx"))
