@@ -841,6 +841,21 @@ int32_t qtx_debug_nop(void* stream);
  * reference counterpart). */
 int32_t qtx_debug_graph_stats(const qtx_model* m, int32_t* entries, int64_t* captures);
 
+/* Which kernel qtx_attention_i8 — and every model-level pass, through the same launcher —
+ * runs for B sentences of H heads, Sq query rows and Sk keys (dec as there; device_counts != 0:
+ * the unfused decode step's form, whose key count and query position are device counters).
+ * Answered by the launcher's own selecting function, nothing is launched.  Returns a
+ * QTX_ATTN_KERNEL_* value, or -1 for a shape the launcher rejects (Sk outside 1 .. 512, or
+ * B, H or Sq below 1).  The kernels' results are bit-identical (test / measurement only, no
+ * reference counterpart). */
+enum {
+  QTX_ATTN_KERNEL_VALU = 0,      /* k_attention: one workgroup per (head, sentence), VALU dots */
+  QTX_ATTN_KERNEL_MFMA = 1,      /* k_attn_mfma: up to 128 keys on the matrix cores */
+  QTX_ATTN_KERNEL_MFMA_LONG = 2  /* k_attn_mfma_long: 129 .. 512 keys on the matrix cores */
+};
+int32_t qtx_debug_attention_kernel(int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t dec,
+                                   int32_t device_counts);
+
 /* Re-read the library's environment switches (csrc/qtx_knobs.h), which are otherwise read
  * once: the path switches the tests use to force the library's alternative code paths
  * (QTX_NO_GRAPH, QTX_UNFUSED, QTX_DECODE_GROUPS, QTX_NO_WSX, ...) and the hooks of the FFN1

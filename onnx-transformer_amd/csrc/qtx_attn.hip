@@ -27,6 +27,7 @@
 // 2-3 in-lane (e), bits 4-5 in-lane (kt).  Keys <= 128.
 #include <cstdlib>
 
+#include "qtx_attn_frag.h"
 #include "qtx_common.h"
 #include "qtx_kernels.h"
 #include "qtx_knobs.h"
@@ -36,29 +37,6 @@ QTX_STAMP_SETTER(attn)
 namespace qtx {
 
 constexpr int AM_MAXK = 128;
-
-// 64-byte K rows, slot swizzle of qtx_gemm.hip (conflict-free ds_read_b128 fragments)
-__device__ __forceinline__ int am_slot(int r, int c) { return c ^ (((r >> 3) & 1) << 1); }
-// staged position of key j (an involution): bits 0-1 <-> bits 2-3
-__device__ __forceinline__ int am_perm(int j) { return (j & ~15) | ((j & 3) << 2) | ((j >> 2) & 3); }
-
-// x + (x of lane ^ 16) / (lane ^ 32): one permlane swap, the pair's sum / max
-__device__ __forceinline__ float xsum16(float v) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float xsum32(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float xmax16(float v) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xmax32(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
 
 template <bool DEC>
 __global__ __launch_bounds__(256) void k_attn_mfma(AttnArgs a) {
@@ -90,21 +68,7 @@ __global__ __launch_bounds__(256) void k_attn_mfma(AttnArgs a) {
 #pragma unroll
     for (int c = 0; c < 4; ++c)
       *reinterpret_cast<uint4*>(Ks + pj * 64 + 16 * am_slot(pj, c)) = ok ? kv[c] : make_uint4(0, 0, 0, 0);
-    // Vt dword (j, f) = bytes v[j][f], v[j][16+f], v[j][32+f], v[j][48+f] (f = 0..15): the PV
-    // B operand of lane (f = lane & 15) for the four 16-wide dim tiles in one ds_read_b32
-    uint32_t* vt = reinterpret_cast<uint32_t*>(Vs + j * 64);
-    const uint32_t* w0 = reinterpret_cast<const uint32_t*>(&vv[0]);
-    const uint32_t* w1 = reinterpret_cast<const uint32_t*>(&vv[1]);
-    const uint32_t* w2 = reinterpret_cast<const uint32_t*>(&vv[2]);
-    const uint32_t* w3 = reinterpret_cast<const uint32_t*>(&vv[3]);
-#pragma unroll
-    for (int f = 0; f < 16; ++f) {
-      const int q = f >> 2, pb = f & 3;
-      const uint32_t sel = (uint32_t)pb | ((uint32_t)(pb + 4) << 8);   // [lo.pb, hi.pb]
-      const uint32_t t01 = __builtin_amdgcn_perm(w1[q], w0[q], sel);
-      const uint32_t t23 = __builtin_amdgcn_perm(w3[q], w2[q], sel);
-      vt[f] = ok ? __builtin_amdgcn_perm(t23, t01, 0x05040100u) : 0u;
-    }
+    am_vt_row(vv, ok, reinterpret_cast<uint32_t*>(Vs + j * 64));   // V transposed (qtx_attn_frag.h)
     const float skj = a.sk[b * a.sk_bs + jc], svj = a.sv[b * a.sv_bs + jc];
     sks[pj] = ok ? skj : 0.0f;
     svs[j] = ok ? svj : 0.0f;
@@ -271,16 +235,6 @@ hipError_t launch_attention_mfma(const AttnArgs& a, hipStream_t st) {
 // instead of every wave re-converting all 128 rows for its own PV (3 VALU per MFMA): the
 // same rounded products float(v) * s_v, so bit-identical; 93.6 -> 85.4 us per launch.
 // =====================================================================================
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_(F& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for_<I + 1, N>(f);
-  }
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_<0, N>(f); }
-
 __device__ __forceinline__ void dma16_lds(const void* gsrc, const void* lds_dst) {
   const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
   unsigned keep;

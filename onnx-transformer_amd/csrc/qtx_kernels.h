@@ -378,6 +378,12 @@ hipError_t launch_step_inc(int* step, hipStream_t st);
 hipError_t launch_nop(hipStream_t st);
 hipError_t launch_gemm256(const GemmArgs& g, hipStream_t st);
 hipError_t launch_attention_mfma(const AttnArgs& a, hipStream_t st);
+// the same attention for 129 .. 512 keys (k_attn_mfma_long, qtx_attn_long.hip);
+// hipErrorNotSupported outside that range and for the sk_dev / qpos_dev forms
+hipError_t launch_attention_mfma_long(const AttnArgs& a, hipStream_t st);
+// which kernel launch_attention runs for a (the values of include/qtx.h's QTX_ATTN_KERNEL_*)
+enum AttnKernel { ATTN_K_VALU = 0, ATTN_K_MFMA = 1, ATTN_K_MFMA_LONG = 2 };
+AttnKernel attention_kernel(const AttnArgs& a);
 // encoder self-attention, all heads of a sentence per workgroup, context quantized per
 // token -> ctx8 (row stride a.c_ld) + sctx; hipErrorNotSupported unless H == 8,
 // Sq == Sk <= 128 and the mask is per key (m_is == 0), and (unless forced) B >= 128

@@ -385,11 +385,21 @@ __global__ __launch_bounds__(256) void k_attention(AttnArgs a) {
   }
 }
 
+// The kernel launch_attention runs for a: the one place that chooses (qtx_debug_attention_kernel
+// reports its answer).  k_attention keeps the device-counter forms of the unfused decode step
+// (sk_dev / qpos_dev) and QTX_ATTN_VALU (QTX_DIAG build: timing experiments).
+AttnKernel attention_kernel(const AttnArgs& a) {
+  if (knobs().attn_valu || a.sk_dev || a.qpos_dev || a.H * 64 > 4096) return ATTN_K_VALU;
+  if (a.Sk <= 128) return ATTN_K_MFMA;
+  return ATTN_K_MFMA_LONG;
+}
+
 hipError_t launch_attention(const AttnArgs& a, hipStream_t st) {
   if (a.B <= 0 || a.Sq <= 0) return hipSuccess;
   if (!a.sk_dev && (a.Sk <= 0 || a.Sk > ATT_MAXK)) return hipErrorInvalidValue;
-  if (!knobs().attn_valu) {              // QTX_ATTN_VALU (QTX_DIAG build): timing experiments
-    const hipError_t e = launch_attention_mfma(a, st);
+  const AttnKernel kern = attention_kernel(a);
+  if (kern != ATTN_K_VALU) {
+    const hipError_t e = kern == ATTN_K_MFMA ? launch_attention_mfma(a, st) : launch_attention_mfma_long(a, st);
     if (e != hipErrorNotSupported) return e;
   }
   k_attention<<<dim3(a.H, a.B), dim3(256), 0, st>>>(a);

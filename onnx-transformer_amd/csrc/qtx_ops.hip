@@ -251,6 +251,18 @@ int32_t qtx_debug_graph_stats(const qtx_model* m, int32_t* entries, int64_t* cap
   return QTX_OK;
 }
 
+int32_t qtx_debug_attention_kernel(int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t dec,
+                                   int32_t device_counts) {
+  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || Sk > 512) return -1;
+  static const int counter = 0;        // stands for the device counters: never dereferenced
+  AttnArgs a{};
+  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.dec = dec != 0;
+  if (device_counts) { a.sk_dev = &counter; a.qpos_dev = &counter; }
+  static_assert(ATTN_K_VALU == QTX_ATTN_KERNEL_VALU && ATTN_K_MFMA == QTX_ATTN_KERNEL_MFMA &&
+                ATTN_K_MFMA_LONG == QTX_ATTN_KERNEL_MFMA_LONG, "include/qtx.h's values");
+  return (int32_t)attention_kernel(a);
+}
+
 int32_t qtx_debug_nop(void* stream) {
   HIPCHK(launch_nop((hipStream_t)stream));
   return QTX_OK;

@@ -143,6 +143,7 @@ SIGNATURES = {
     "qtx_decode_generator": (I32, [P, P, I32, P, P, P]),
     "qtx_debug_nop": (I32, [P]),
     "qtx_debug_graph_stats": (I32, [P, C.POINTER(I32), C.POINTER(I64)]),
+    "qtx_debug_attention_kernel": (I32, [I32, I32, I32, I32, I32, I32]),
     "qtx_debug_reload_knobs": (I32, []),
     "qtx_model_check": (I32, [P, P]),
 }
@@ -187,6 +188,17 @@ def call(name, *args):
     if rc != 0:
         raise QtxError(name, rc, L.qtx_last_error().decode(errors="replace"))
     return rc
+
+
+ATTN_KERNELS = ("k_attention", "k_attn_mfma", "k_attn_mfma_long")   # QTX_ATTN_KERNEL_* of qtx.h
+
+
+def attention_kernel(B, H, Sq, Sk, dec=0, device_counts=0) -> str:
+    """The attention kernel a shape reaches (qtx_debug_attention_kernel), by name."""
+    k = lib().qtx_debug_attention_kernel(B, H, Sq, Sk, dec, device_counts)
+    if not 0 <= k < len(ATTN_KERNELS):
+        raise ValueError(f"no attention kernel takes B={B} H={H} Sq={Sq} Sk={Sk}")
+    return ATTN_KERNELS[k]
 
 
 def reload_knobs():
