@@ -82,10 +82,12 @@ typedef struct qtx_model qtx_model;
  * max_len: the rows of the positional table.  Every decoder-side entry takes up to 512 target
  * positions and never more than the table holds (the same for S).  qtx_greedy_decode and
  * qtx_greedy_decode_scored run the fused step and its graphs at every such shape (past 128
- * keys with the four-wave attention kernel, qtx_decode_attention below); the fault, trials,
- * beam and score drivers run the fused step up to S, max_len <= 128 and the unfused step and
+ * keys with the four-wave attention kernel, qtx_decode_attention below), and so does
+ * qtx_beam_decode (past 128 target positions without moving a cache:
+ * qtx_decode_attention_beam, qtx_beam_ancestry of qtx_beam_long.h); the fault, trials
+ * and score drivers run the fused step up to S, max_len <= 128 and the unfused step and
  * the generic attention kernel from 129 on (supported shapes;
- * tests/test_gpu_long_fused.py, tests/test_gpu_long_target.py). */
+ * tests/test_gpu_long_fused.py, tests/test_gpu_beam_long.py, tests/test_gpu_long_target.py). */
 typedef struct {
   int32_t src_vocab, tgt_vocab, n_layers, d_model, d_ff, n_heads, max_len, weight_bits;
 } qtx_config;
@@ -480,7 +482,9 @@ int32_t qtx_greedy_decode_kvtrials(const qtx_model* m, const int64_t* src, const
  * The encoder and the cross K/V GEMM run once on the B sentences.  The step is the greedy
  * decode's on B * K rows — the fused step where the greedy decode would take it, else the
  * unfused one, so every config qtx_model_create accepts beam-decodes — with the tail replaced
- * by k_beam_select and k_beam_reorder (csrc/qtx_decode.hip; the caches are permuted in place).
+ * by k_beam_select and k_beam_reorder (csrc/qtx_decode.hip; the caches are permuted in place)
+ * or, on the fused step with max_len > 128 and beam > 1, by k_beam_select and k_beam_ancestry
+ * (csrc/qtx_decode_beam.hip: a byte table of slots is permuted, the caches stay).
  * Steps run in chunks of QTX_GRAPH_STEPS (default 8): the fused step as captured graphs of
  * that many steps and of one step (graphs of their own; QTX_NO_GRAPH and the unfused step run
  * eager); one group (QTX_DECODE_GROUPS is ignored).  early_exit != 0: after each chunk but the

@@ -576,13 +576,18 @@ DecAttnArgs dec_attn_cross(const GreedyWS& g, int l, int B, int S, const uint8_t
 }
 
 // The beam step's tail on the step's R = B * beam rows: the selection (scores, parents, tokens,
-// next inputs, position + 1, rows still live), then the caches of every layer by parent.
+// next inputs, position + 1, rows still live), then the caches of every layer by parent — or,
+// on the ancestry path (max_len > 128), the rows of the ancestry table alone, in one launch.
 int beam_tail(const qtx_model* m, GreedyWS& g, int R, int max_len, hipStream_t st) {
   const qtx_config& c = m->cfg;
   const BeamTail& b = *g.beam;
   HIPCHK(launch_beam_select(g.logits, R / b.K, b.K, c.tgt_vocab, b.eos, b.pad, max_len, g.step,
                             b.st.score, b.st.fin, b.st.len, b.st.parent, b.st.bp_par,
                             b.st.bp_tok, m->tgt_lut, m->pe, c.max_len, g.dec.x, st));
+  if (b.ancestry) {
+    HIPCHK(launch_beam_ancestry(b.anc, R / b.K, b.K, max_len, g.step, b.st.parent, st));
+    return QTX_OK;
+  }
   HIPCHK(launch_beam_reorder(b.kc0, b.vc0, b.skc0, b.svc0, R / b.K, b.K, max_len, c.n_layers,
                              b.k_ls, b.v_ls, b.s_ls, b.grouped ? 1 : 0, g.step, b.st.parent, st));
   return QTX_OK;
@@ -670,8 +675,11 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
     }
     DecAttnArgs at = dec_attn_self(g, l, B, max_len, host_pos ? t_host + 1 : 0);
     at.pmax = own_max ? nullptr : g.pmax_a;
-    QTX_RUN(4, launch_dec_attn(at, B, st));
-    a = skinny(wb, L.o, B, own_max ? A_F32R : A_F32Q, EPI_RESIDUAL, s.x, D);   // quantizes ctx per token
+    if (g.beam && g.beam->ancestry)   // cached rows through the ancestry table (no reorder)
+      QTX_RUN(4, launch_dec_attn_beam(at, g.beam->anc, g.beam->K, B, st));
+    else
+      QTX_RUN(4, launch_dec_attn(at, B, st));
+    a = skinny(wb, L.o,B, own_max ? A_F32R : A_F32Q, EPI_RESIDUAL, s.x, D);   // quantizes ctx per token
     a.X = s.ctx; a.ldx = D; a.pmax_in = g.pmax_a; a.pmax_n = 8; a.res = s.x; a.ldr = D;
     QTX_RUN(16, launch_skinny(a, wb, st));
     RC(ln_linear(L.cq, L.ln[1], 0, s.y, D, 2));
@@ -838,13 +846,15 @@ int decoder_body(const qtx_model* m, Scratch& s, const CrossKV& x, const uint8_t
   return QTX_OK;
 }
 
-// whether the decode runs the fused step (else the unfused one): the fault, trials, beam and
-// score drivers, whose own attention kernels and cache handling stop at 128 keys
+// whether the decode runs the fused step (else the unfused one): the fault, trials and score
+// drivers, whose own attention kernels and cache handling stop at 128 keys
 bool greedy_fused(const qtx_config& c, int S, int max_len) {
   return S <= 128 && max_len <= 128 && fused_step_ok(c) && !knobs().unfused;
 }
 // the same for the plain and the scored greedy decode, whose step needs nothing but
-// launch_dec_attn past 128 keys: every decode shape (k_dec_attn_long from key 129 on)
+// launch_dec_attn past 128 keys: every decode shape (k_dec_attn_long from key 129 on).  The
+// beam decode decides with it too: past 128 target positions its step reads the self caches
+// through the ancestry table (k_dec_attn_beam) and moves no cache (qtx_search.hip)
 bool greedy_fused_long(const qtx_config& c, int S, int max_len) {
   return S <= 512 && max_len <= 512 && fused_step_ok(c) && !knobs().unfused;
 }

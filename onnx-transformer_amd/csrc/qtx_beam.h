@@ -60,6 +60,21 @@ QTX_HD inline BeamGeom::Chunk BeamGeom::locate(int n, long i) const {
   return {BEAM_NONE, 0};
 }
 
+// The ancestry table of the beam decode past 128 positions (k_dec_attn_beam, k_beam_ancestry:
+// qtx_decode_beam.hip): uint8 [B * beam][max_len], entry [b * beam + k][j] = the slot of
+// sentence b whose cache row holds position j of hypothesis k.  In place of moving the caches,
+// a step permutes the valid prefix of the table's rows by parent: thread i of a sentence owns
+// byte offset i of all its rows.
+struct AncGeom {
+  int max_len;
+  QTX_HD size_t bytes(size_t rows) const { return rows * (size_t)max_len; }
+  // thread i of a sentence at n valid positions -> the offset it owns in every row; -1: none
+  QTX_HD long owner(int n, long i) const {
+    const int c = n < 0 ? 0 : (n > max_len ? max_len : n);
+    return i >= 0 && i < c ? i : -1;
+  }
+};
+
 // The search state of R = B * beam rows (include/qtx.h, beam search): carved from an arena
 // with `template <class T> T* take(size_t n)`.
 struct BeamState {

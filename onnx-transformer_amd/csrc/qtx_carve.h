@@ -107,6 +107,10 @@ struct BeamTail {
   float *skc0 = nullptr, *svc0 = nullptr;
   long k_ls = 0, v_ls = 0, s_ls = 0;
   bool grouped = true;   // V in the fused step's 4-key groups (else [max_len][512])
+  // the ancestry table [R][max_len] (qtx_beam.h AncGeom) and whether the decode runs on it
+  // (fused step, max_len > 128, K > 1: k_dec_attn_beam + k_beam_ancestry, no reorder)
+  uint8_t* anc = nullptr;
+  bool ancestry = false;
 };
 
 // The fused decode runs the batch as up to QTX_MAX_GROUPS independent sub-batches, each a
@@ -274,6 +278,7 @@ inline BeamWS carve_beam(Arena& ar, const qtx_config& c, int B, int K, int S, in
   g.mask = ar.take<uint8_t>(R * S);
   w.mask_b = ar.take<uint8_t>((size_t)B * S);
   w.tail.st = carve_beam_state(ar, B, K, max_len);
+  w.tail.anc = ar.take<uint8_t>(AncGeom{max_len}.bytes(R));
   w.tail.K = K;
   return w;
 }

@@ -339,6 +339,17 @@ hipError_t launch_beam_select(const float* logits, int B, int K, int V, int eos,
 hipError_t launch_beam_reorder(int8_t* kc, int8_t* vc, float* skc, float* svc, int B, int K,
                                int max_len, int L, long k_ls, long v_ls, long s_ls, int grouped,
                                const int* step, const int* parent, hipStream_t st);
+// The beam decode past 128 positions (qtx_decode_beam.hip): no cache moves; anc [B*K][max_len]
+// uint8 holds, per row and position, the slot whose cache row holds it (qtx_beam.h AncGeom).
+//   dec_attn_beam: k_dec_attn_long's self form (a.kv_new, 1 .. 512 rows) for B = sentences * K
+//                  rows, cached rows read through anc (a.kv_bs = the table's row length); the
+//                  append goes to the row's own slot.  1 <= K <= BEAM_MAXK, B % K == 0.
+//   ancestry:      anc rows of slot j := its parent's over the step[0] valid positions, in place
+//   anc_init:      anc[b * K + k][j] = k
+hipError_t launch_dec_attn_beam(const DecAttnArgs& a, const uint8_t* anc, int K, int B, hipStream_t st);
+hipError_t launch_beam_ancestry(uint8_t* anc, int B, int K, int max_len, const int* step,
+                                const int* parent, hipStream_t st);
+hipError_t launch_beam_anc_init(uint8_t* anc, int B, int K, int max_len, hipStream_t st);
 hipError_t launch_beam_rep(const void* in, void* out, int B, int K, long bytes, hipStream_t st);
 hipError_t launch_beam_init(int B, int K, float* score, int* fin, int* len, int* parent,
                             int* step, hipStream_t st);

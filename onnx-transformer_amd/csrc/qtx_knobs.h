@@ -62,6 +62,9 @@ struct Knobs {
                                         // the device counter even where the host knows it
   QTX_DKNOB(bool, int4_packed, false);  // QTX_INT4_PACKED: a 4-bit model's decode step on the
                                         // packed int4 kernels
+  QTX_DKNOB(bool, beam_reorder_long, false);  // QTX_BEAM_REORDER_LONG: the beam decode past 128
+                                        // positions on k_dec_attn_long + k_beam_reorder (the
+                                        // caches moved every step) instead of the ancestry table
   // QTX_FFN_FUSED_MIN_M: the encoder's fused FFN launch (k_ffn_fused) from this many rows
   // (default off — measured slower than the split launches at cfg3, DESIGN.md §4 "The fused
   // FFN kernel"; the product keeps it as the C-ABI entry qtx_ffn_rows only);

@@ -51,6 +51,7 @@ Knobs read_env() {
   k.hquant_rows = flag("QTX_HQUANT_ROWS");
   k.device_step = flag("QTX_DEVICE_STEP");
   k.int4_packed = flag("QTX_INT4_PACKED");
+  k.beam_reorder_long = flag("QTX_BEAM_REORDER_LONG");
   k.no_ffn_fused = flag("QTX_NO_FFN_FUSED");
   k.ffn_fused_min_m = num("QTX_FFN_FUSED_MIN_M", 1L << 40);
   k.ablate = (int)num("QTX_ABLATE", 0);

@@ -1,12 +1,14 @@
 // qtx_search.hip — the beam-search decode with EOS stop (qtx_beam_decode) and the
 // teacher-forced target scoring (qtx_score_targets) of the C-ABI (include/qtx.h), with their
-// per-op entries.  Both run the encoder once on the B sentences and replicate its cross K/V to
-// their rows; the workspaces are carved by qtx_carve.h.
+// per-op entries (the beam search past 128 positions: include/qtx_beam_long.h).  Both run the
+// encoder once on the B sentences and replicate its cross K/V to their rows; the workspaces are
+// carved by qtx_carve.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <vector>
 
+#include "../../include/qtx_beam_long.h"
 #include "qtx_host.h"
 
 namespace qtx {
@@ -30,9 +32,10 @@ int replicate_cross(const qtx_config& c, const CrossKV& src, CrossKV& dst, int B
 }
 
 // What precedes the steps: the encoder and the cross K/V GEMM once on the B sentences, their
-// results replicated to the B * K hypotheses, the search state and the first decoder input.
+// results replicated to the B * K hypotheses, the search state (on the ancestry path: every
+// table entry the row's own slot) and the first decoder input.
 int beam_prologue(const qtx_model* m, BeamWS& w, const int64_t* src, int B, int K, int S,
-                  int64_t start, bool fused, hipStream_t st) {
+                  int max_len, int64_t start, bool fused, hipStream_t st) {
   const qtx_config& c = m->cfg;
   GreedyWS& g = w.g;
   RC(encode_src(m, g, src, w.mask_b, B, S, w.cross_b, fused ? w.cvg_b : nullptr, nullptr, st));
@@ -40,6 +43,7 @@ int beam_prologue(const qtx_model* m, BeamWS& w, const int64_t* src, int B, int 
   HIPCHK(launch_beam_rep(w.mask_b, g.mask, B, K, S, st));
   const BeamState& bs = w.tail.st;
   HIPCHK(launch_beam_init(B, K, bs.score, bs.fin, bs.len, bs.parent, g.step, st));
+  if (w.tail.ancestry) HIPCHK(launch_beam_anc_init(w.tail.anc, B, K, max_len, st));
   HIPCHK(launch_fill_col(bs.ids0, 1, B * K, start, st));
   HIPCHK(launch_embed(bs.ids0, 1, B * K, 1, nullptr, 0, m->tgt_lut, c.tgt_vocab, m->pe, c.max_len,
                       g.dec.x, c.d_model, st));
@@ -101,13 +105,18 @@ int32_t qtx_beam_decode(const qtx_model* m, const int64_t* src, const uint8_t* s
   BeamWS w = carve_beam(fr.ar, c, B, beam, S, max_len);
   w.tail.eos = (int)eos; w.tail.pad = (int)pad;
   const int R = B * beam;
-  // every config decodes: the fused step where the greedy decode of R rows would take it
-  const bool fused = greedy_fused(c, S, max_len);
+  // every config decodes: the fused step where the greedy decode of R rows would take it.
+  // Past 128 target positions the fused step reads the self caches through the ancestry table
+  // and the tail permutes that table, not the caches (beam 1 has nothing to permute and stays
+  // on the plain kernels; up to 128 positions: k_dec_attn and the reorder, whatever S is).
+  // The choice follows from max_len, beam and the switches, all in the step graphs' key.
+  const bool fused = greedy_fused_long(c, S, max_len);
   w.tail.grouped = fused;
+  w.tail.ancestry = fused && max_len > 128 && beam > 1 && !knobs().beam_reorder_long;
   w.g.beam = &w.tail;
   w.g.enc.status = fr.status;
   HIPCHK(hipMemcpyAsync(w.mask_b, src_mask, (size_t)B * S, hipMemcpyDeviceToDevice, st));
-  RC(beam_prologue(m, w, src, B, beam, S, start, fused, st));
+  RC(beam_prologue(m, w, src, B, beam, S, max_len, start, fused, st));
   // the steps in chunks of QTX_GRAPH_STEPS (default 8); with early_exit the rows still live
   // are read back after each chunk (one 4-byte synchronising copy) and the decode stops at 0
   const int total = max_len - 1, big = graph_chunk();
@@ -164,6 +173,33 @@ int32_t qtx_beam_reorder(int8_t* kc, int8_t* vc, float* skc, float* svc, int32_t
                                "16-byte aligned");
   HIPCHK(launch_beam_reorder(kc, vc, skc, svc, B, beam, max_len, n_layers, k_ls, v_ls, s_ls,
                              g.grouped, step_dev, parent, (hipStream_t)stream));
+  return QTX_OK;
+}
+
+int32_t qtx_decode_attention_beam(const float* y, int64_t ldy, int8_t* kc, int8_t* vc, float* skc,
+                                  float* svc, int32_t kv_bs, const int32_t* step_dev,
+                                  const uint8_t* anc, int32_t beam, int32_t B, float* ctx,
+                                  float* pmax, void* stream) {
+  if (!y || !kc || !vc || !skc || !svc || !ctx || !pmax || !step_dev || !anc)
+    return fail(QTX_E_INVALID, "null argument");
+  if (kv_bs <= 0 || kv_bs > 512 || beam < 1 || beam > BEAM_MAXK || B < 0 || B % beam)
+    return fail(QTX_E_INVALID, "beam decode attention: kv_bs %d, beam %d, B %d", kv_bs, beam, B);
+  if (!aligned16(y) || !aligned16(kc) || !aligned16(vc) || ldy % 4 || ldy < 1536)
+    return fail(QTX_E_INVALID, "beam decode attention: y / kc / vc must be 16-byte aligned, "
+                               "ldy %% 4 == 0 and ldy >= 1536 (ldy=%ld)", (long)ldy);
+  DecAttnArgs a{};
+  a.y = y; a.ldy = ldy; a.kc = kc; a.vc = vc; a.skc = skc; a.svc = svc; a.kv_bs = kv_bs;
+  a.step = step_dev; a.kv_new = 1; a.ctx = ctx; a.pmax = pmax; a.B = B;
+  HIPCHK(launch_dec_attn_beam(a, anc, beam, B, (hipStream_t)stream));
+  return QTX_OK;
+}
+
+int32_t qtx_beam_ancestry(uint8_t* anc, int32_t B, int32_t beam, int32_t max_len,
+                          const int32_t* step_dev, const int32_t* parent, void* stream) {
+  if (!anc || !step_dev || !parent) return fail(QTX_E_INVALID, "null argument");
+  if (B <= 0 || B > 65535 || beam < 1 || beam > BEAM_MAXK || max_len < 1 || max_len > 512)
+    return fail(QTX_E_INVALID, "beam ancestry: bad shape B=%d beam=%d max_len=%d", B, beam, max_len);
+  HIPCHK(launch_beam_ancestry(anc, B, beam, max_len, step_dev, parent, (hipStream_t)stream));
   return QTX_OK;
 }
 

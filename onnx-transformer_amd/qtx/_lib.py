@@ -155,6 +155,12 @@ SIGNATURES_ENCTRIALS = {
     "qtx_greedy_decode_enctrials": (I32, [P, P, P, I32, I32, I32, I64, P, P, P, P, SZ, FP, P]),
 }
 
+# the same for include/qtx_beam_long.h
+SIGNATURES_BEAM_LONG = {
+    "qtx_decode_attention_beam": (I32, [P, I64, P, P, P, P, I32, P, P, I32, I32, P, P, P]),
+    "qtx_beam_ancestry": (I32, [P, I32, I32, I32, P, P, P]),
+}
+
 
 def header_symbols(path=None) -> list[str]:
     """Function names declared in include/qtx.h (used by the ABI test)."""
@@ -174,7 +180,7 @@ def lib(build: bool = True):
     if not os.path.exists(path):
         raise RuntimeError(f"libqtx.so missing at {path}; run __graft_entry__.build()")
     L = C.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **SIGNATURES_ENCTRIALS}.items():
+    for name, (res, args) in {**SIGNATURES, **SIGNATURES_ENCTRIALS, **SIGNATURES_BEAM_LONG}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     _lib = L

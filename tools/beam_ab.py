@@ -12,6 +12,16 @@ two beam kernels (profiles/beam_ab.md).  Not wired into bench.py.
         k_beam_select and k_beam_reorder alone: 50 launches each in one captured graph at
         cfg2's shape (128 rows, the model's vocabulary, 6 layers), us per launch, at
         positions 8 / 36 / 70 and with an identity / a shuffled parent vector.
+    python tools/beam_ab.py long [--lib PATH] [--rounds 5]
+        the beam decode past 128 keys (profiles/beam_long_ab.md): the default model with a
+        512-row positional table, B = 32, beam = 4, early_exit off, at (S, max_len) =
+        (72, 140), (72, 512), (200, 72); alternating rounds, medians.  --lib: the parent commit's
+        build (these shapes unfused), or the diagnostic build with QTX_BEAM_REORDER_LONG=1 (the
+        fused step on k_dec_attn_long with the caches reordered every step).
+    python tools/beam_ab.py long-kernels
+        what one step pays either way at 130 and 500 cached positions of max_len 512 (128 rows,
+        6 layers), us per launch in a captured graph: k_beam_reorder against k_beam_ancestry,
+        k_dec_attn_long against k_dec_attn_beam (one-slot and all-mixed tables).
 """
 import argparse
 import ctypes as C
@@ -78,6 +88,101 @@ def decode(args):
               f"({med * 1e3 / (L - 1):7.1f} us/step, {len(v)} rounds)", flush=True)
 
 
+def long_decode(args):
+    import torch
+    if args.lib:
+        os.environ["QTX_LIB_PATH"] = args.lib
+        from qtx import _lib
+        old = C.CDLL(args.lib)
+        _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(old, k)}
+    from qtx.model import QtxModel, to_u8_mask
+    from qtx.weights import ModelConfig, synthetic_state_dict
+    cfg = ModelConfig(max_len=512)
+    model = QtxModel(synthetic_state_dict(20241223, cfg), cfg)
+    rng = np.random.default_rng(11)
+    dev, B = model.device, 32
+    cases = {}
+    for S, L in ((72, 140), (72, 512), (200, 72)):
+        src = make_src(rng, B, S)
+        s = torch.from_numpy(src).to(dev)
+        m = to_u8_mask((src != 2)[:, None, :], dev).reshape(B, S)
+        cases[(S, L)] = lambda s=s, m=m, L=L: model.beam(s, m, max_len=L, beam_size=4, early_exit=False)
+    for fn in cases.values():          # warm-up: graph capture, workspace growth
+        for _ in range(2):
+            fn()
+    times = {k: [] for k in cases}
+    for _ in range(args.rounds):       # alternating rounds
+        for k, fn in cases.items():
+            times[k].append(timed(fn, torch))
+    for (S, L), v in times.items():
+        med = statistics.median(v)
+        print(f"beam B=32 beam=4 S={S:3d} max_len={L:3d} median {med:9.3f} ms  min {min(v):9.3f}  "
+              f"max {max(v):9.3f}  ({med * 1e3 / (L - 1):7.1f} us/step, {len(v)} rounds)", flush=True)
+
+
+def graph_us(torch, fn, N=50):
+    """us per launch of fn(stream), N back-to-back launches in one captured graph, 10 replays."""
+    g, s = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        fn(C.c_void_p(s.cuda_stream))
+        s.synchronize()
+        with torch.cuda.graph(g, stream=s):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            for _ in range(N):
+                fn(st)
+    for _ in range(3):
+        g.replay()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(10):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / 10 / N
+
+
+def long_kernels(args):
+    import torch
+    from qtx import _lib
+    lib = _lib.lib(build=False)
+    B, K, ML, NL = 32, 4, 512, 6
+    R, G4 = B * K, ML // 4
+    P = lambda t: C.c_void_p(t.data_ptr())
+    rng = np.random.default_rng(0)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    kc = torch.randint(-127, 128, (NL, R, ML * 512), dtype=torch.int8, device="cuda")
+    vc = torch.randint(-127, 128, (NL, R, G4 * 2048), dtype=torch.int8, device="cuda")
+    skc = torch.full((NL, R, ML), 0.01, dtype=torch.float32, device="cuda")
+    svc = torch.full((NL, R, ML), 0.01, dtype=torch.float32, device="cuda")
+    y = T(rng.standard_normal((R, 1536)).astype(np.float32))
+    ctx = torch.zeros((R, 512), dtype=torch.float32, device="cuda")
+    pm = torch.zeros((8, R), dtype=torch.float32, device="cuda")
+    parent = T(np.tile(np.array([1, 0, 0, 2], np.int32), B))
+    slot, j = np.arange(K)[:, None], np.arange(ML)[None, :]
+    tables = {"one slot": np.tile(np.broadcast_to(slot, (K, ML)), (B, 1)),
+              "all mixed": np.tile((slot + j) % K, (B, 1))}
+    for pos in (130, 500):             # cached positions; the step's own position is pos
+        step = T(np.array([pos, 0, 0, 0], np.int32))
+        us = graph_us(torch, lambda st: lib.qtx_beam_reorder(
+            P(kc), P(vc), P(skc), P(svc), B, K, ML, NL, R * ML * 512, R * G4 * 2048, R * ML, 1,
+            P(step), P(parent), st))
+        print(f"{pos:3d} positions  k_beam_reorder (6 layers, parents 1 0 0 2) {us:8.2f} us", flush=True)
+        anc = T(tables["all mixed"].astype(np.uint8))
+        us = graph_us(torch, lambda st: lib.qtx_beam_ancestry(P(anc), B, K, ML, P(step), P(parent), st))
+        print(f"{pos:3d} positions  k_beam_ancestry (parents 1 0 0 2)          {us:8.2f} us", flush=True)
+        us = graph_us(torch, lambda st: lib.qtx_decode_attention(
+            1, P(y), 1536, P(kc[0]), P(vc[0]), P(skc[0]), P(svc[0]), ML, P(step), 0, None, R, P(ctx),
+            P(pm), st))
+        print(f"{pos:3d} positions  k_dec_attn_long (one layer)                 {us:8.2f} us", flush=True)
+        for name, t in tables.items():
+            anc = T(t.astype(np.uint8))
+            us = graph_us(torch, lambda st: lib.qtx_decode_attention_beam(
+                P(y), 1536, P(kc[0]), P(vc[0]), P(skc[0]), P(svc[0]), ML, P(step), P(anc), K, R,
+                P(ctx), P(pm), st))
+            print(f"{pos:3d} positions  k_dec_attn_beam (one layer, {name:9s})      {us:8.2f} us", flush=True)
+
+
 def kernels(args):
     import torch
     from qtx import _lib
@@ -98,34 +203,12 @@ def kernels(args):
     svc = torch.zeros((NL, R, ML), dtype=torch.float32, device="cuda")
     bp = torch.zeros((2, ML - 1, R), dtype=torch.int32, device="cuda")
     x = torch.zeros((R, 512), dtype=torch.float32, device="cuda")
-    N = 50
-
-    def graph_us(fn):
-        g, s = torch.cuda.CUDAGraph(), torch.cuda.Stream()
-        with torch.cuda.stream(s):
-            fn(C.c_void_p(s.cuda_stream))
-            s.synchronize()
-            with torch.cuda.graph(g, stream=s):
-                st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-                for _ in range(N):
-                    fn(st)
-        for _ in range(3):
-            g.replay()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / 10 / N
-
     for pos in (8, 36, 70):
         for name, par in (("identity", np.tile(np.arange(K), B)),
                           ("shuffled", np.tile(np.array([1, 0, 0, 2]), B))):
             step = T(np.array([pos, 0, 0, 0], np.int32))
             parent = T(par.astype(np.int32))
-            us = graph_us(lambda st: lib.qtx_beam_reorder(
+            us = graph_us(torch, lambda st: lib.qtx_beam_reorder(
                 P(kc), P(vc), P(skc), P(svc), B, K, ML, NL, R * krow, R * vrow, R * ML, 1, P(step),
                 P(parent), st))
             print(f"k_beam_reorder pos {pos:2d} {name:8s} {us:7.2f} us", flush=True)
@@ -136,20 +219,20 @@ def kernels(args):
     parent = torch.zeros((R,), dtype=torch.int32, device="cuda")
     step = T(np.array([8, 0, 0, 0], np.int32))
     logits[:, V - 1] = float("-inf")   # eos = V - 1 is never selected: every row stays live
-    us = graph_us(lambda st: lib.qtx_beam_select(model.handle, P(logits), B, K, V - 1, V - 2, ML, P(step),
+    us = graph_us(torch, lambda st: lib.qtx_beam_select(model.handle, P(logits), B, K, V - 1, V - 2, ML, P(step),
                                                 P(score), P(fin), P(ln), P(parent), P(bp[0]),
                                                 P(bp[1]), P(x), st))
     print(f"k_beam_select  B {B} beam {K} V {V}: {us:7.2f} us", flush=True)
-    us = graph_us(lambda st: lib.qtx_debug_nop(st))
+    us = graph_us(torch, lambda st: lib.qtx_debug_nop(st))
     print(f"empty kernel (dependent-launch floor): {us:7.2f} us", flush=True)
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["decode", "kernels"])
+    ap.add_argument("what", choices=["decode", "kernels", "long", "long-kernels"])
     ap.add_argument("--lib", default=None)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--no-beam", action="store_true",
                     help="decode: the greedy lines only (this build against --lib, like for like)")
     a = ap.parse_args()
-    decode(a) if a.what == "decode" else kernels(a)
+    {"decode": decode, "kernels": kernels, "long": long_decode, "long-kernels": long_kernels}[a.what](a)

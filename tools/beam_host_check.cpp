@@ -10,7 +10,9 @@
 // workspace (carve_beam, csrc/qtx_carve.h) for several (config, B, beam, S, max_len), from a
 // real allocation of exactly the computed size, checks the regions disjoint and the layer
 // strides against BeamGeom's rows, and writes every carved byte (an overlap or a short size
-// is an ASan / check failure); (3) checks the argument limits.
+// is an ASan / check failure); (3) checks the argument limits; (4) replays k_beam_ancestry's
+// ownership (AncGeom::owner, the function the kernel indexes with) on a host copy of the
+// ancestry table: one owner per byte, the prefix equal to a gather, the rest untouched.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -128,6 +130,8 @@ static void workspace_case(const qtx_config& c, int B, int K, int S, int max_len
   r.add("score", st.score, R); r.add("fin", st.fin, R); r.add("len", st.len, R);
   r.add("parent", st.parent, R); r.add("bp_par", st.bp_par, T * R); r.add("bp_tok", st.bp_tok, T * R);
   r.add("ids0", st.ids0, R);
+  r.add("anc", w.tail.anc, AncGeom{max_len}.bytes(R));   // the ancestry table [R][max_len]
+  CHECK(!w.tail.ancestry);                               // the driver's choice, not the carving's
   // inside the allocation, pairwise disjoint
   std::vector<Region> v = r.v;
   std::sort(v.begin(), v.end(), [](const Region& a, const Region& b) { return a.p < b.p; });
@@ -211,6 +215,34 @@ static void reorder_case(int max_len, int grouped, int K, const std::vector<int>
   }
 }
 
+// k_beam_ancestry on the host: thread i of the launch grid (ceil(max_len / 256) blocks of 256
+// per sentence) owns offset AncGeom::owner(n, i) of the sentence's K table rows.
+static void ancestry_case(int max_len, int K, const std::vector<int>& parent, int n_in) {
+  const AncGeom g{max_len};
+  const int n = n_in < 0 ? 0 : std::min(n_in, max_len);
+  std::vector<uint8_t> anc(g.bytes(K)), own(g.bytes(K), 0);
+  unsigned seed = 777u + n + 5 * K;
+  for (auto& b : anc) { seed = seed * 1664525u + 1013904223u; b = (uint8_t)((seed >> 24) % K); }
+  const auto anc0 = anc;
+  long owners = 0;
+  for (long i = -1; i < (long)((max_len + 255) / 256) * 256; ++i) {
+    const long off = g.owner(n_in, i);
+    if (off < 0) continue;
+    CHECK(off == i && off < n);
+    ++owners;
+    uint8_t ch[BEAM_MAXK];
+    for (int j = 0; j < K; ++j) ch[j] = anc[(size_t)j * max_len + off];
+    for (int j = 0; j < K; ++j) {
+      anc[(size_t)j * max_len + off] = ch[parent[j]];
+      CHECK(++own[(size_t)j * max_len + off] == 1);
+    }
+  }
+  CHECK(owners == n);
+  for (int j = 0; j < K; ++j)
+    for (int e = 0; e < max_len; ++e)
+      CHECK(anc[(size_t)j * max_len + e] == anc0[(size_t)(e < n ? parent[j] : j) * max_len + e]);
+}
+
 static void carve_case(int B, int K, int max_len) {
   Arena size;
   carve_beam_state(size, B, K, max_len);
@@ -238,6 +270,10 @@ int main() {
       for (const auto& p : parents)
         for (int n : {-3, 0, 1, 3, 4, 5, max_len - 1, max_len, max_len + 9})
           reorder_case(max_len, grouped, (int)p.size(), p, n);
+  for (int max_len : {1, 5, 140, 256, 257, 512})
+    for (const auto& p : parents)
+      for (int n : {-3, 0, 1, 4, 130, 255, 256, max_len - 1, max_len, max_len + 9})
+        ancestry_case(max_len, (int)p.size(), p, n);
   for (int B : {1, 3, 32})
     for (int K : {1, 3, 8})
       for (int max_len : {1, 2, 14, 72}) carve_case(B, K, max_len);
@@ -252,6 +288,8 @@ int main() {
           for (int max_len : {1, 2, 13, 14, 16}) workspace_case(*c, B, K, S, max_len);
   workspace_case(full, 32, 4, 72, 72);
   workspace_case(full, 5, 8, 71, 73);
+  workspace_case(small, 2, 3, 9, 140);      // past 128 positions: the table's rows are read
+  workspace_case(wide, 3, 8, 130, 512);
   // limits: (B, beam, V, start, eos, pad) -> 0 ok / 1 invalid / 4 unsupported
   CHECK(beam_limits(4, 4, 97, 0, 1, 2) == 0);
   CHECK(beam_limits(4, 1, 97, 0, 1, 2) == 0 && beam_limits(4, 8, 97, 0, 1, 2) == 0);
