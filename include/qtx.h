@@ -77,7 +77,9 @@ typedef struct qtx_model qtx_model;
  * Every config qtx_model_create accepts runs every model-level call (tests/
  * test_gpu_model_configs.py; the kernel chain per config: DESIGN.md, supported shapes):
  * the row-GEMM encoder / decoder chain needs d_ff % 512 == 0, the fused decode step
- * d_ff 512 or 2048 and tgt_vocab <= 8192; any other config takes the generic chain and the
+ * d_ff 512 or 2048 and tgt_vocab <= 65536 (qtx_greedy_decode, qtx_greedy_decode_scored and
+ * qtx_beam_decode; above 8192 words with the streamed tails of qtx_wide_vocab.h) or <= 8192
+ * (the fault, trials and score drivers); any other config takes the generic chain and the
  * unfused step, with the same results.
  * max_len: the rows of the positional table.  Every decoder-side entry takes up to 512 target
  * positions and never more than the table holds (the same for S).  qtx_greedy_decode and
@@ -253,9 +255,11 @@ int32_t qtx_greedy_decode_fault(const qtx_model* m, const int64_t* src,
  * ids[:, 1:].  fault: NULL or an encoder fault.  Same path selection as the plain decode
  * (fused step with graphs, eager, sub-batches, graphs of several steps, unfused step; the
  * scored step has its own captured graphs).  The fused step's tail (csrc/qtx_decode.hip
- * k_top2_embed) takes tgt_vocab <= 8192, as the plain one: a model with a larger vocabulary
- * decodes, plain and scored, with the unfused step, whose tail has no cap (the per-op
- * qtx_decode_argmax_embed / qtx_decode_top2_embed keep the cap).  B * tgt_vocab < 2^30.
+ * k_top2_embed) takes tgt_vocab <= 8192, as the plain one; a model of up to 65536 words still
+ * decodes, plain and scored, with the fused step, which then ends with the streamed tails of
+ * qtx_wide_vocab.h (csrc/qtx_decode_wide.hip), and a larger one with the unfused step, whose
+ * tail has no cap (the per-op qtx_decode_argmax_embed / qtx_decode_top2_embed keep the cap of
+ * 8192).  B * tgt_vocab < 2^30.
  * Writes exactly ids [B, max_len], top_ids and top_logp [B, max_len-1, 2].
  * ws: qtx_greedy_scored_workspace_size bytes (qtx_greedy_workspace_size is unchanged).
  * QTX_E_UNSUPPORTED with the diagnostic QTX_DBG_TAIL switch. */

@@ -545,10 +545,16 @@ Groups decode_groups(int B) {   // (Groups / split_groups, no empty group: qtx_c
 // ---- fused decode step (M = B rows, keys <= 512) ----------------------------------------
 // Its kernels exist for the flagship shapes only: the skinny GEMM takes K = 512 or 2048
 // (FFN2: K = d_ff; launch_skinny) and the argmax / top-2 tails a vocabulary of at most
-// ARG_MAXV.  Every other config qtx_model_create accepts decodes with the unfused step,
-// whose kernels have no such limit (greedy_run decides before anything is captured).
+// ARG_MAXV — WIDE_MAXV with the streamed tails (k_tok_wide / k_top2_wide), which the plain,
+// scored and beam decodes' step takes above ARG_MAXV (fused_step_wide_ok; the fault, trials and
+// score drivers keep fused_step_ok).  Every other config qtx_model_create accepts decodes with
+// the unfused step, whose kernels have no such limit (greedy_run decides before anything is
+// captured).
 bool fused_step_ok(const qtx_config& c) {
   return (c.d_ff == 512 || c.d_ff == 2048) && c.tgt_vocab <= ARG_MAXV;
+}
+bool fused_step_wide_ok(const qtx_config& c) {
+  return (c.d_ff == 512 || c.d_ff == 2048) && c.tgt_vocab <= WIDE_MAXV;
 }
 
 SkinnyArgs skinny(int wbits, const QLin& L, int M, int amode, int flags, float* out, long ldo) {
@@ -624,8 +630,13 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
   // and from step 1 on layer 0's LN+QKV launch decides the previous step's token from them,
   // embeds it and stores ids / x itself (launch_skinny_tok) — a step is then 49 launches.
   // Only the last step still ends with the argmax kernel.
+  // Above ARG_MAXV words nothing is folded (k_skinny_wide_tok holds a row's records in one
+  // wave): the plain step ends with k_tok_wide on the same records, the scored one with
+  // k_top2_wide.
+  const bool wide = c.tgt_vocab > ARG_MAXV;
   const bool fold = !knobs().no_tail_fold && host_pos && !g.top_ids && wb == 8 && fused_ln &&
-                    !knobs().ablate && !knobs().dbg_tail && !g.no_fold && !g.beam;
+                    !knobs().ablate && !knobs().dbg_tail && !g.no_fold && !g.beam && !wide;
+  const bool tok_wide = wide && !g.top_ids && !g.beam;
   Scratch& s = g.dec;
   // Timing experiments only (wrong results): QTX_ABLATE=<bitmask> drops kernel classes
   // from the step (replaced by an empty kernel with QTX_ABLATE_NOP=1) to measure what
@@ -716,10 +727,19 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
     return QTX_OK;
   }
   QTX_RUN(256, launch_generator_mfma(s.x, D, B, m->dec_norm[0], m->dec_norm[1], m->gen_wt,
-                                     m->gen_b, c.tgt_vocab, g.logits, st, fold ? g.rec : nullptr));
+                                     m->gen_b, c.tgt_vocab, g.logits, st,
+                                     fold || tok_wide ? g.rec : nullptr));
   if (fold && t_host + 2 < max_len) return QTX_OK;   // the next step's first launch is the tail
   if (g.beam) return beam_tail(m, g, B, max_len, st);
-  if (g.top_ids)   // scored decode: the tail that also writes the step's two best (id, logp)
+  unsigned* const arrive = reinterpret_cast<unsigned*>(g.step + 1);
+  if (wide && g.top_ids)
+    QTX_RUN(256, launch_top2_wide(g.logits, B, c.tgt_vocab, ids, max_len, g.top_ids, g.top_logp,
+                                  g.step, arrive, m->tgt_lut, m->pe, c.max_len, s.x, st,
+                                  host_pos ? t_host + 1 : 0));
+  else if (wide)
+    QTX_RUN(256, launch_tok_wide(g.rec, g.logits, B, c.tgt_vocab, ids, max_len, g.step, arrive,
+                                 m->tgt_lut, m->pe, c.max_len, s.x, st, host_pos ? t_host + 1 : 0));
+  else if (g.top_ids)   // scored decode: the tail that also writes the step's two best (id, logp)
     QTX_RUN(256, launch_top2_embed(g.logits, B, c.tgt_vocab, ids, max_len, g.top_ids, g.top_logp,
                                    g.step, reinterpret_cast<unsigned*>(g.step + 1), m->tgt_lut,
                                    m->pe, c.max_len, s.x, st, host_pos ? t_host + 1 : 0));
@@ -854,9 +874,11 @@ bool greedy_fused(const qtx_config& c, int S, int max_len) {
 // the same for the plain and the scored greedy decode, whose step needs nothing but
 // launch_dec_attn past 128 keys: every decode shape (k_dec_attn_long from key 129 on).  The
 // beam decode decides with it too: past 128 target positions its step reads the self caches
-// through the ancestry table (k_dec_attn_beam) and moves no cache (qtx_search.hip)
+// through the ancestry table (k_dec_attn_beam) and moves no cache (qtx_search.hip).  These three
+// also take vocabularies of up to WIDE_MAXV words (greedy_step_fused's streamed tails; the beam
+// tail reads the logits from global memory at any width)
 bool greedy_fused_long(const qtx_config& c, int S, int max_len) {
-  return S <= 512 && max_len <= 512 && fused_step_ok(c) && !knobs().unfused;
+  return S <= 512 && max_len <= 512 && fused_step_wide_ok(c) && !knobs().unfused;
 }
 
 int regroup_cross_values(const qtx_config& c, const CrossKV& x, int B, int S, int8_t* cvg,

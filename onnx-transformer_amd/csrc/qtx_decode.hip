@@ -23,6 +23,7 @@
 #include "qtx_decode_ka.h"
 #include "qtx_kernels.h"
 #include "qtx_knobs.h"
+#include "qtx_tail.h"
 
 QTX_STAMP_SETTER(decode)
 
@@ -1368,19 +1369,7 @@ hipError_t launch_transpose(const float* in, int R, int Cc, float* out, hipStrea
 // =====================================================================================
 constexpr int ARG_T = 1024, ARG_NV = 8;
 static_assert(ARG_MAXV == ARG_T * ARG_NV, "the row of logits in the workgroup's registers");
-constexpr float ARG_DELTA = 4.0e-6f;   // >= 2 ulp(16): covers every V <= ARG_MAXV
-
-__device__ __forceinline__ int wave_sum_i32(int v) {
-  auto d = [](int x, auto ctrl) {
-    return __builtin_amdgcn_update_dpp(0, x, decltype(ctrl)::value, 0xF, 0xF, true);
-  };
-  v += d(v, std::integral_constant<int, 0xB1>{});
-  v += d(v, std::integral_constant<int, 0x4E>{});
-  v += d(v, std::integral_constant<int, 0x141>{});
-  v += d(v, std::integral_constant<int, 0x140>{});
-  return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
-         (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
-}
+// (ARG_DELTA, wave_sum_i32: qtx_tail.h)
 
 // host_s1: the position + 1 when the host knows it (then no read of *step and no step
 // advance: nothing of a decode whose every step knows its position reads the counter);
@@ -1535,23 +1524,7 @@ struct TkTail {
   const float* ln_a; const float* ln_b; const float* bias; const float* logits;
   float* out; float* xres; int64_t* ids; long ids_bs; int pos, ldo;
 };
-struct TokRec { float m1, m2; int i1, fl; };
-// the record of the union of two disjoint sets: m1 by "larger value, then smaller index", m2
-// the largest of the loser's m1 and both m2, flags or'ed (commutative and associative)
-__device__ __forceinline__ void tok_merge(TokRec& a, float m1, float m2, int i1, int fl) {
-  const bool lead = (m1 > a.m1) | ((m1 == a.m1) & (i1 < a.i1));   // (no branches)
-  const float loser = lead ? a.m1 : m1;
-  a.m2 = fmaxf(fmaxf(a.m2, m2), loser);
-  a.m1 = lead ? m1 : a.m1;
-  a.i1 = lead ? i1 : a.i1;
-  a.fl |= fl;
-}
-template <int CTRL>
-__device__ __forceinline__ void tok_merge_dpp(TokRec& a) {   // (the partner lane's set is disjoint)
-  const float m1 = dpp<CTRL>(a.m1), m2 = dpp<CTRL>(a.m2);
-  const int i1 = dpp_i32<CTRL>(a.i1), fl = dpp_i32<CTRL>(a.fl);
-  tok_merge(a, m1, m2, i1, fl);
-}
+// (TokRec, tok_merge, tok_merge_dpp: qtx_tail.h)
 // the first argmax of logp = (x - mx) - lse over one row of logits, one wave
 __device__ __forceinline__ int tok_exact(const float* row, int V, float mx, int lane) {
   float ls = 0.0f;

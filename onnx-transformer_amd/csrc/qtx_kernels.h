@@ -262,9 +262,12 @@ hipError_t launch_pack_gen(const float* W, int V, float* out, hipStream_t st);
 // log_softmax + argmax + next-token embedding + step increment (decode tail):
 //   ids[m, *step + 1] = argmax;  xnext[m] = lut[id]*sqrt(512) + pe[*step + 1];
 //   the last workgroup to finish advances *step (arrive is its private counter).
-// V <= ARG_MAXV (this and launch_top2_embed: hipErrorInvalidValue above it; a model with a
-// larger vocabulary decodes with launch_logsoftmax_argmax / _top2, which have no cap).
+// V <= ARG_MAXV (this, launch_top2_embed and launch_skinny_tok: hipErrorInvalidValue above it;
+// the fused step of a model with up to WIDE_MAXV words ends with launch_tok_wide /
+// launch_top2_wide below, every other decode of a larger vocabulary with
+// launch_logsoftmax_argmax / _top2, which have no cap).
 constexpr int ARG_MAXV = 8192;
+constexpr int WIDE_MAXV = 65536;
 hipError_t launch_argmax_embed(const float* logits, int M, int V, int64_t* ids, long ids_bs,
                                int* step, unsigned* arrive, const float* lut, const float* pe,
                                int max_pos, float* xnext, hipStream_t st, int host_s1 = 0);
@@ -274,6 +277,19 @@ hipError_t launch_top2_embed(const float* logits, int M, int V, int64_t* ids, lo
                              int64_t* top_ids, float* top_logp, int* step, unsigned* arrive,
                              const float* lut, const float* pe, int max_pos, float* xnext,
                              hipStream_t st, int host_s1 = 0);
+// The same two tails for a row that fits neither registers nor LDS (qtx_decode_wide.hip):
+// identical outputs, position / counter contract and argument rules, for V <= WIDE_MAXV.
+//   tok_wide:  1 <= V; decides from rec, the generator's per-strip records of the same logits
+//              (launch_generator_mfma), and reads the logits only for a near-tie
+//   top2_wide: 2 <= V; three streamed passes over the logits
+hipError_t launch_tok_wide(const float* rec, const float* logits, int M, int V, int64_t* ids,
+                           long ids_bs, int* step, unsigned* arrive, const float* lut,
+                           const float* pe, int max_pos, float* xnext, hipStream_t st,
+                           int host_s1 = 0);
+hipError_t launch_top2_wide(const float* logits, int M, int V, int64_t* ids, long ids_bs,
+                            int64_t* top_ids, float* top_logp, int* step, unsigned* arrive,
+                            const float* lut, const float* pe, int max_pos, float* xnext,
+                            hipStream_t st, int host_s1 = 0);
 // The decoder-fault decode's small kernels (csrc/qtx_decode.hip).  rec_ids int64 / rec_logp
 // float [B][2][2]: [b][0] the golden, [b][1] the faulty top 2 of the corrupted step.
 //   gold: rec[b][0] = entry (b, step) of top_ids / top_logp [B][top_bs][2]

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <mutex>
 
+#include "../../include/qtx_wide_vocab.h"
 #include "qtx_host.h"
 
 namespace qtx {
@@ -306,6 +307,34 @@ int32_t qtx_decode_top2_embed(const qtx_model* m, const float* logits, int32_t M
                                          m->tgt_lut, m->pe, c.max_len, x_next,
                                          (hipStream_t)stream),
                   "tgt_vocab %d", c.tgt_vocab);
+}
+
+// ---- the same two tails for up to WIDE_MAXV words (include/qtx_wide_vocab.h) -------------
+int32_t qtx_decode_tok_wide(const qtx_model* m, const float* logits, const float* rec, int32_t M,
+                            int64_t* ids, int64_t ids_bs, int32_t* step_dev, float* x_next,
+                            void* stream) {
+  if (!m || !logits || !rec || !ids || !step_dev || !x_next) return fail(QTX_E_INVALID, "null argument");
+  if (M <= 0) return QTX_OK;
+  if (!aligned16(rec)) return fail(QTX_E_INVALID, "rec must be 16-byte aligned");
+  const qtx_config& c = m->cfg;
+  return launched(launch_tok_wide(rec, logits, M, c.tgt_vocab, ids, ids_bs, step_dev,
+                                  reinterpret_cast<unsigned*>(step_dev + 1), m->tgt_lut, m->pe,
+                                  c.max_len, x_next, (hipStream_t)stream),
+                  "tgt_vocab %d (1 .. %d), M * tgt_vocab < 2^30", c.tgt_vocab, WIDE_MAXV);
+}
+
+int32_t qtx_decode_top2_wide(const qtx_model* m, const float* logits, int32_t M, int64_t* ids,
+                             int64_t ids_bs, int64_t* top_ids, float* top_logp,
+                             int32_t* step_dev, float* x_next, void* stream) {
+  if (!m || !logits || !ids || !top_ids || !top_logp || !step_dev || !x_next)
+    return fail(QTX_E_INVALID, "null argument");
+  const qtx_config& c = m->cfg;
+  RC(check_top2_vocab(c));
+  if (M <= 0) return QTX_OK;
+  return launched(launch_top2_wide(logits, M, c.tgt_vocab, ids, ids_bs, top_ids, top_logp,
+                                   step_dev, reinterpret_cast<unsigned*>(step_dev + 1),
+                                   m->tgt_lut, m->pe, c.max_len, x_next, (hipStream_t)stream),
+                  "tgt_vocab %d (2 .. %d), M * tgt_vocab < 2^30", c.tgt_vocab, WIDE_MAXV);
 }
 
 int32_t qtx_pack_int4(const int8_t* q, int32_t N, int32_t K, uint8_t* packed, void* stream) {

@@ -161,6 +161,12 @@ SIGNATURES_BEAM_LONG = {
     "qtx_beam_ancestry": (I32, [P, I32, I32, I32, P, P, P]),
 }
 
+# the same for include/qtx_wide_vocab.h
+SIGNATURES_WIDE_VOCAB = {
+    "qtx_decode_tok_wide": (I32, [P, P, P, I32, P, I64, P, P, P]),
+    "qtx_decode_top2_wide": (I32, [P, P, I32, P, I64, P, P, P, P, P]),
+}
+
 
 def header_symbols(path=None) -> list[str]:
     """Function names declared in include/qtx.h (used by the ABI test)."""
@@ -180,7 +186,8 @@ def lib(build: bool = True):
     if not os.path.exists(path):
         raise RuntimeError(f"libqtx.so missing at {path}; run __graft_entry__.build()")
     L = C.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **SIGNATURES_ENCTRIALS, **SIGNATURES_BEAM_LONG}.items():
+    for name, (res, args) in {**SIGNATURES, **SIGNATURES_ENCTRIALS, **SIGNATURES_BEAM_LONG,
+                              **SIGNATURES_WIDE_VOCAB}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     _lib = L
