@@ -747,7 +747,9 @@ int32_t qtx_pack_w_ws(const int8_t* W, int32_t N, int32_t K, int8_t* out, void* 
  * N % 16 == 0, K in {512, 2048} (amode 1: K = 512); M * max(ldx, K), M * N and N * K below
  * 2^30 (the kernels address their operands with 32-bit byte offsets), else QTX_E_UNSUPPORTED.
  * Supported flags: 0, 1, 2 and 1|4 (every other combination: QTX_E_UNSUPPORTED, nothing
- * written).  X rows are ldx floats apart and read in 16-byte vectors: X (amode 0: A) and W
+ * written).  K in {256, 768, 1024, 1280, 1536, 1792} (FFN2 of a model with d_ff = K) is taken
+ * with weight_bits 8, amode 0, 2 or 3 and flags 0 or 2 only (anything else there:
+ * QTX_E_UNSUPPORTED, nothing written).  X rows are ldx floats apart and read in 16-byte vectors: X (amode 0: A) and W
  * 16-byte aligned, ldx % 4 == 0, ldx >= K, else QTX_E_INVALID; only the K floats of a row and
  * the pmax_n * M partial maxima are used.
  * quant_linear.py:111-119, layer_norm.py:12-15. */

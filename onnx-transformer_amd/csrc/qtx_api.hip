@@ -543,19 +543,22 @@ Groups decode_groups(int B) {   // (Groups / split_groups, no empty group: qtx_c
 }
 
 // ---- fused decode step (M = B rows, keys <= 512) ----------------------------------------
-// Its kernels exist for the flagship shapes only: the skinny GEMM takes K = 512 or 2048
-// (FFN2: K = d_ff; launch_skinny) and the argmax / top-2 tails a vocabulary of at most
-// ARG_MAXV — WIDE_MAXV with the streamed tails (k_tok_wide / k_top2_wide), which the plain,
+// Its kernels take every feed-forward width qtx_model_create accepts — FFN2 is the one GEMM of
+// the step with K = d_ff: K = 512 and 2048 in qtx_decode.hip, the six other multiples of 256 in
+// qtx_decode_dff.hip (launch_skinny) — and, in the argmax / top-2 tails, a vocabulary of at
+// most ARG_MAXV — WIDE_MAXV with the streamed tails (k_tok_wide / k_top2_wide), which the plain,
 // scored and beam decodes' step takes above ARG_MAXV (fused_step_wide_ok; the fault, trials and
-// score drivers keep fused_step_ok).  Every other config qtx_model_create accepts decodes with
-// the unfused step, whose kernels have no such limit (greedy_run decides before anything is
-// captured).
-bool fused_step_ok(const qtx_config& c) {
-  return (c.d_ff == 512 || c.d_ff == 2048) && c.tgt_vocab <= ARG_MAXV;
+// score drivers keep fused_step_ok).  One exception: the diagnostic build's packed-int4 step
+// (QTX_INT4_PACKED on a 4-bit model) has 4-bit FFN2 kernels for K = 512 and 2048 alone.  Every
+// other config qtx_model_create accepts decodes with the unfused step, whose kernels have no
+// such limit (greedy_run decides before anything is captured).
+static bool fused_dff_ok(const qtx_config& c) {
+  if (c.d_ff == 512 || c.d_ff == 2048) return true;
+  return c.d_ff % 256 == 0 && c.d_ff >= 256 && c.d_ff < 2048 &&
+         !(c.weight_bits == 4 && knobs().int4_packed);
 }
-bool fused_step_wide_ok(const qtx_config& c) {
-  return (c.d_ff == 512 || c.d_ff == 2048) && c.tgt_vocab <= WIDE_MAXV;
-}
+bool fused_step_ok(const qtx_config& c) { return fused_dff_ok(c) && c.tgt_vocab <= ARG_MAXV; }
+bool fused_step_wide_ok(const qtx_config& c) { return fused_dff_ok(c) && c.tgt_vocab <= WIDE_MAXV; }
 
 SkinnyArgs skinny(int wbits, const QLin& L, int M, int amode, int flags, float* out, long ldo) {
   SkinnyArgs s{};

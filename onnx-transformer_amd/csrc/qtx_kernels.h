@@ -236,6 +236,10 @@ hipError_t launch_pack_ffn(const int8_t* W1, const int8_t* W2, int F, int8_t* ou
 
 hipError_t launch_gemm(const GemmArgs& a, int wbits, hipStream_t st);
 hipError_t launch_skinny(const SkinnyArgs& a, int wbits, hipStream_t st);
+// its kernels for K = 256 q, q = 1, 3 .. 7 (FFN2 of a model with d_ff = K; qtx_decode_dff.hip):
+// 8-bit weights, amode A_I8 / A_F32Q / A_F32R, flags 0 or EPI_RESIDUAL, else
+// hipErrorInvalidValue (a validated by launch_skinny, which dispatches here)
+hipError_t launch_skinny_dff(const SkinnyArgs& a, hipStream_t st);
 hipError_t launch_dec_attn(const DecAttnArgs& a, int B, hipStream_t st);
 // its kernel for 129 .. 512 rows to load (four waves per (sentence, head); a validated by
 // launch_dec_attn, which dispatches here)

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 REPO = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "libqtx.so")
-SOURCES = ["qtx_kernels.hip", "qtx_decode.hip", "qtx_decode_long.hip", "qtx_decode_beam.hip", "qtx_decode_wide.hip", "qtx_gemm.hip", "qtx_wsgemm.hip", "qtx_attn.hip",
+SOURCES = ["qtx_kernels.hip", "qtx_decode.hip", "qtx_decode_long.hip", "qtx_decode_beam.hip", "qtx_decode_wide.hip", "qtx_decode_dff.hip", "qtx_gemm.hip", "qtx_wsgemm.hip", "qtx_attn.hip",
            "qtx_attn_long.hip",
            "qtx_ffn.hip", "qtx_model.hip", "qtx_api.hip", "qtx_fault.hip", "qtx_search.hip",
            "qtx_ops.hip", "qtx_knobs.hip", "qtx_rowfault.hip", "qtx_trials.hip", "qtx_enctrials.hip"]
@@ -21,7 +21,7 @@ SOURCES = ["qtx_kernels.hip", "qtx_decode.hip", "qtx_decode_long.hip", "qtx_deco
 # library (build(extra=...) -> libqtx_diag.so, with -DQTX_DIAG), never into libqtx.so
 DIAG_SOURCES = ["diag/qtx_wsgemm_diag.hip"]   # csrc/diag/: outside the product sources
 HEADERS = ["qtx_common.h", "qtx_kernels.h", "qtx_ws.h", "qtx_knobs.h", "qtx_beam.h", "qtx_carve.h",
-           "qtx_stepgraph.h", "qtx_host.h", "qtx_decode_ka.h", "qtx_attn_frag.h", "qtx_tail.h"]
+           "qtx_stepgraph.h", "qtx_host.h", "qtx_decode_ka.h", "qtx_attn_frag.h", "qtx_tail.h", "qtx_skinny.h"]
 
 # -ffp-contract=off: every float op is a separate IEEE op (the numerics contract,
 # DESIGN.md §3); HIP keeps correctly rounded fp32 '/' and sqrtf by default.
@@ -39,6 +39,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 # fp32 ops only.  (qtx_decode.hip keeps its flags: its code object is the benchmark's.)
 # qtx_decode_beam.hip (that attention for beam rows, through the ancestry table): both, likewise.
 # qtx_decode_wide.hip (the step's tails above 8192 words): both, likewise.
+# qtx_decode_dff.hip (the step's FFN2 for d_ff = 256, 768 .. 1792): both, likewise.
 # qtx_attn_long.hip (attention past 128 keys): no packed fp32 instructions, for the same reason.
 _PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
@@ -46,6 +47,7 @@ SOURCE_FLAGS = {"qtx_decode.hip": _PRELOAD,
                 "qtx_decode_long.hip": _PRELOAD + _NO_PK_F32,
                 "qtx_decode_beam.hip": _PRELOAD + _NO_PK_F32,
                 "qtx_decode_wide.hip": _PRELOAD + _NO_PK_F32,
+                "qtx_decode_dff.hip": _PRELOAD + _NO_PK_F32,
                 "qtx_attn_long.hip": _NO_PK_F32}
 
 
