@@ -51,7 +51,8 @@ def operands(seed, M, N, K, lo, flip):
 
 
 # (lo, flip) per K: the conditions they meet are stated and checked in test_big_acc_ref.py
-PARAMS = {2048: (96, 0.02), 1280: (120, 0.01), 1344: (120, 0.01)}
+PARAMS = {2048: (96, 0.02), 1280: (120, 0.01), 1344: (120, 0.01), 1536: (120, 0.01),
+          1792: (120, 0.01)}
 SEED = 1
 
 
@@ -71,6 +72,22 @@ def to_float_half_away(acc):
     rem = np.abs(a) - np.abs(t.astype(np.float64)).astype(np.int64)
     gap = (np.abs(up.astype(np.float64)) - np.abs(t.astype(np.float64))).astype(np.int64)
     return np.where(2 * rem >= gap, np.where(rem == 0, t, up), t).astype(f32)
+
+
+def wave8_fp32_sum(qx, qw):
+    """float(acc) as a wrong k_skinny8_dff would form it: k-step s (64 columns) of the K / 64
+    goes to wave s mod 8, each wave's int32 partial (exact, below 2^24) is converted to fp32,
+    and the partials are added in fp32 in wave order.  Every addition that reaches 2^24 rounds,
+    so the result differs from one rounding of the exact sum."""
+    qx, qw = np.asarray(qx, np.int64), np.asarray(qw, np.int64)
+    K = qx.shape[1]
+    steps = np.einsum("msk,nsk->smn", qx.reshape(len(qx), K // 64, 64), qw.reshape(len(qw), K // 64, 64))
+    tot = np.zeros(steps.shape[1:], f32)
+    for w in range(min(8, K // 64)):
+        part = steps[w::8].sum(0)
+        assert np.abs(part).max() < TWO24            # exact in fp32
+        tot = (tot + part.astype(f32)).astype(f32)
+    return tot
 
 
 def stats(acc):

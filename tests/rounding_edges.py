@@ -160,6 +160,29 @@ def discrimination(x, n_bits=8, relu=False):
 LONE_MODELS = (("a", 0), ("b_lo", -1), ("b_hi", +1))
 
 
+def _lone_row(D, idx, col):
+    """Row idx of a lone-row family at width D: its near-tie at column col, one that model
+    LONE_MODELS[idx % 3] gets wrong, the (mantissa, exponent) sets taken in turn."""
+    t = idx % 3
+    mant, exp = COMBOS[idx % len(COMBOS)]
+    s = scale_of(mant, exp)
+    k = (np.arange(D) * 37 + idx) % 253 - 126
+    row = _exact32(float(s) * k.astype(np.float64))
+    row[(col + 130) % D] = f32(127.0) * s
+    pat, kk = tie_pattern(mant, exp)
+    cand = pat[kk >= 0].reshape(-1)
+    ref = np.rint(cand / s)
+    wrong = model_recip(cand[None], np.array([s]), LONE_MODELS[t][1])[0] != ref
+    assert wrong.any()
+    y = f32(1.0) / s
+    for _ in range(abs(LONE_MODELS[t][1])):
+        y = np.nextafter(y, f32(np.inf) if LONE_MODELS[t][1] > 0 else f32(0))
+    r = (cand * y).astype(f32).astype(np.float64)
+    dist = np.where(wrong, np.abs(r - np.floor(r) - 0.5), -1.0)
+    row[col] = cand[np.argmax(dist)]
+    return row
+
+
 @functools.lru_cache(maxsize=None)
 def lone_rows(D):
     """(rows f32 [3 * D/64, D], cols int, models): row 3 * slot + t holds its lone near-tie at
@@ -171,27 +194,62 @@ def lone_rows(D):
     out = np.empty((n, D), f32)
     cols = np.empty(n, np.int64)
     for idx in range(n):
-        slot, t = divmod(idx, 3)
-        mant, exp = COMBOS[idx % len(COMBOS)]
-        s = scale_of(mant, exp)
+        slot = idx // 3
         lane = (11 * idx + 5) % 64
         col = 256 * (slot // 4) + 4 * lane + slot % 4
-        k = (np.arange(D) * 37 + idx) % 253 - 126
-        row = _exact32(float(s) * k.astype(np.float64))
-        row[(col + 130) % D] = f32(127.0) * s
-        pat, kk = tie_pattern(mant, exp)
-        cand = pat[kk >= 0].reshape(-1)
-        ref = np.rint(cand / s)
-        wrong = model_recip(cand[None], np.array([s]), LONE_MODELS[t][1])[0] != ref
-        assert wrong.any()
-        y = f32(1.0) / s
-        for _ in range(abs(LONE_MODELS[t][1])):
-            y = np.nextafter(y, f32(np.inf) if LONE_MODELS[t][1] > 0 else f32(0))
-        r = (cand * y).astype(f32).astype(np.float64)
-        dist = np.where(wrong, np.abs(r - np.floor(r) - 0.5), -1.0)
-        row[col] = cand[np.argmax(dist)]
-        out[idx], cols[idx] = row, col
+        out[idx], cols[idx] = _lone_row(D, idx, col), col
     return _ro(out), _ro(cols), tuple(m for _ in range(D // 64) for m, _ in LONE_MODELS)
+
+
+# k_skinny8_dff (K = 256 Q) holds a row differently: waves 2 r and 2 r + 1 take one half of row
+# r each (half h starts at column 128 Q h), and within the half load c of lane l holds VW
+# consecutive floats from column VW (l + 64 c): VW = 4 and Q / 2 loads for even Q, VW = 2 and Q
+# loads for odd Q, whose last load shares its dword of codes with two zero fillers.
+DFF_KS = (256, 768, 1024, 1280, 1536, 1792)
+
+
+def dff8_slot(K, col):
+    """(half, load, lane, element) that holds column col of a row in k_skinny8_dff."""
+    Q = K // 256
+    vw = 4 if Q % 2 == 0 else 2
+    h, o = divmod(int(col), 128 * Q)
+    chunk, e = divmod(o, vw)
+    c, lane = divmod(chunk, 64)
+    return h, c, lane, e
+
+
+def dff8_col(K, h, c, lane, e):
+    Q = K // 256
+    vw = 4 if Q % 2 == 0 else 2
+    return 128 * Q * h + vw * (lane + 64 * c) + e
+
+
+@functools.lru_cache(maxsize=None)
+def lone_rows_dff8(K):
+    """lone_rows(K) and, after them, rows built the same way (_lone_row: the same sets and
+    models in turn) for what lone_rows(K) leaves out of k_skinny8_dff's layout: every (half,
+    load, element) it does not visit, at a lane strictly between 0 and 63, and lanes 0 and 63
+    of either half (in the half's last load) where no row has its near-tie there.
+    Returns (rows, cols, models) as lone_rows."""
+    rows, cols, models = lone_rows(K)
+    Q = K // 256
+    vw, nc = (4, Q // 2) if Q % 2 == 0 else (2, Q)
+    seen = [dff8_slot(K, c) for c in cols]
+    add = []
+    for h in range(2):
+        for c in range(nc):
+            for e in range(vw):
+                if not any((h, c, e) == (s[0], s[1], s[3]) for s in seen):
+                    add.append(dff8_col(K, h, c, 1 + (7 * len(add) + 12) % 62, e))
+    for h in range(2):
+        for lane in (0, 63):
+            if not any((h, lane) == (s[0], s[2]) for s in seen):
+                add.append(dff8_col(K, h, nc - 1, lane, (h + lane) % vw))
+    n = len(rows)
+    more = [_lone_row(K, n + i, col) for i, col in enumerate(add)]
+    out = np.concatenate([rows, np.array(more, f32).reshape(len(more), K)])
+    return (_ro(out), _ro(np.concatenate([cols, np.array(add, np.int64)])),
+            models + tuple(LONE_MODELS[(n + i) % 3][0] for i in range(len(add))))
 
 
 # ------------------------------------------------------------------ constructions
@@ -203,6 +261,13 @@ SKINNY_DIRECT = tuple((amode, K, nparts, M, (M + K // 512 + nparts) % len(COMBOS
                       for amode, K, nparts in ((3, 512, 0), (3, 2048, 0), (2, 512, 8),
                                                (2, 2048, 128), (2, 2048, 32))
                       for M in (3, 40, 100))
+# the same for the FFN2 widths of csrc/qtx_decode_dff.hip: amode 3, and amode 2 with the step's
+# K / 16 partial maxima and with the 8-wave kernel's limit of 128; M = 3 runs k_skinny8_dff (one
+# ragged block), 40 k_skinny's 4-row blocks, 100 its 8-row blocks
+SKINNY_DFF = tuple((amode, K, nparts, M, (M + K // 256 + nparts) % len(COMBOS))
+                   for K in DFF_KS
+                   for amode, nparts in ((3, 0), (2, K // 16), (2, 128))
+                   for M in (3, 40, 100))
 # (start, kind) of each call of a GEMM-epilogue case (onehot_gemm)
 ONEHOT_QKV = (tuple((s, "ties") for s in (0, 3, 6, 9, 12, 15))
               + ((2, "lone"), (13, "lone"), (4, "bias"), (11, "bias")))

@@ -98,6 +98,46 @@ def test_k1344_accumulators_are_ties():
     assert st["vs_trunc"] >= 0.40 and st["vs_half_away"] >= 0.40
 
 
+@pytest.mark.parametrize("K", [1536, 1792])
+def test_k1536_k1792_accumulators_are_ties(K):
+    """K = 1536 and 1792 (the widest FFN2 of csrc/qtx_decode_dff.hip), lo = 120, flip = 0.01 as
+    K = 1280, M x N = 37 x 64, seed 1, under K = 2048's bounds.  Measured, K = 1536: |acc| in
+    [21,911,555, 22,915,569], 48.8 % odd, half negative, astype(float32) differs from truncation
+    on 52.7 % and from round-half-away on 47.3 % of the odd ones; K = 1792: [25,582,148,
+    26,874,120], 49.1 % odd, half negative, 49.5 % and 50.5 %."""
+    _, _, acc = _acc(37, 64, K)
+    st = BA.stats(acc)
+    assert BA.TWO24 <= st["min_abs"] and st["max_abs"] < 2 * BA.TWO24
+    assert st["odd_big"] >= 0.40
+    assert st["negative"] == 0.5
+    assert (acc[:, 0::2] > 0).all() and (acc[:, 1::2] < 0).all()
+    assert st["vs_trunc"] >= 0.40 and st["vs_half_away"] >= 0.40
+
+
+@pytest.mark.parametrize("K", [1280, 1536, 1792])
+@pytest.mark.parametrize("M", [5, 40, 100, 200])
+def test_every_dff_gpu_shape_is_in_range(K, M):
+    """The shapes of test_gpu_big_acc.py::test_skinny_dff (N = 512): all in [2^24, 2^25), at
+    least 40 % odd, both conversions told apart on at least 40 % of the odd ones."""
+    _, _, acc = _acc(M, 512, K)
+    st = BA.stats(acc)
+    assert BA.TWO24 <= st["min_abs"] and st["max_abs"] < 2 * BA.TWO24 and st["odd_big"] >= 0.40
+    assert st["negative"] == 0.5
+    assert st["vs_trunc"] >= 0.40 and st["vs_half_away"] >= 0.40
+
+
+@pytest.mark.parametrize("K", [1280, 1536, 1792])
+def test_wave8_fp32_partials_differ(K):
+    """One more wrong model, k_skinny8_dff's own split (BA.wave8_fp32_sum): the K / 64 k-steps
+    dealt round-robin to 8 waves, each wave's int32 partial — below 2^24, so exact — converted
+    to fp32 and the partials added in fp32 in wave order.  On the M = 5, N = 512 case (the one
+    that runs the 8-wave kernel) it differs from astype(float32) of the exact sum on 18.9 % of
+    the outputs at K = 1280, 32.7 % at 1536 and 41.3 % at 1792 (asserted: at least one)."""
+    qx, qw, acc = _acc(5, 512, K)
+    wrong = BA.wave8_fp32_sum(qx, qw) != acc.astype(np.int32).astype(f32)
+    assert wrong.any()
+
+
 @pytest.mark.parametrize("M,N", [(257, 272), (5, 512), (40, 512), (100, 512), (200, 512),
                                  (7, 512), (129, 512)])
 def test_every_gpu_shape_is_in_range(M, N):

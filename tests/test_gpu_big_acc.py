@@ -170,6 +170,30 @@ def test_skinny(gb, oracle_model, amode, M):
     gb.assert_poison(pm, "pmax_out")
 
 
+@pytest.mark.parametrize("M", [5, 40, 100, 200])
+@pytest.mark.parametrize("amode", [0, 2, 3])
+@pytest.mark.parametrize("K", [1280, 1536, 1792])
+def test_skinny_dff(gb, oracle_model, K, amode, M):
+    """test_skinny at the FFN2 widths above 1041 of csrc/qtx_decode_dff.hip.  M = 5, amode 2 / 3:
+    k_skinny8_dff, whose 8 waves (K / 64 = 20, 24, 28 k-steps dealt round-robin) each hold an
+    int32 partial below 2^24 that wave 0 sums through LDS — a sum or conversion of the partials
+    in fp32 differs on 19 % to 41 % of these outputs (tests/test_big_acc_ref.py); M = 40 / 100 /
+    200 and amode 0: k_skinny at the new K with 4- / 8- or 16- / 16-row blocks.  amode 2 takes
+    the step's K / 16 partial maxima."""
+    N = 512
+    r = dict(case(M, N, K) if amode == 0 else fp32_case(M, N, K))
+    r["n"] = K // 16 if amode == 2 else 0
+    r["parts"] = None
+    if amode == 2:
+        r["parts"] = np.abs(r["x"]).reshape(M, r["n"], 16).max(-1).T.astype(f32)
+    rc, out, pm = _skinny_run(gb, r, amode, M, N, K, 8, RESID)
+    assert_ok(rc, "qtx_skinny_linear")
+    gb.check()
+    y = r["res"] + O.linear_epilogue(r["acc"], r["sx"], r["sw"], r["b"])
+    np.testing.assert_array_equal(np_(out), y)
+    gb.assert_poison(pm, "pmax_out")
+
+
 # =====================================================================================
 # qtx_ffn_rows, F = 2048: the fused kernel's second accumulator
 # =====================================================================================

@@ -3,7 +3,9 @@
 fused_step_ok in csrc/qtx_api.hip) against the oracle, bit for bit.
 
 1. FFN2 per op (qtx_skinny_linear, N = 512, residual): M = 1 and 5 run k_skinny8_dff (5: a
-   ragged second block), M = 33 k_skinny's 4-row blocks, M = 97 its 8- / 16-row blocks.
+   ragged second block), M = 33 k_skinny's 4-row blocks, M = 97 its 8- / 16-row blocks; at three
+   K also without the residual flag and with N = 48.  Every case in guarded buffers at both
+   alignments (test_gpu_bounds.py's gb fixture).
 2. Plain, scored and beam decodes of the two-layer models on every path, with capture counts.
 3. The fault drivers (kvfault, cached dfault, kvtrials) at d_ff 768 (odd q) and 1024: their
    golden steps are now the fused step, the faulty step stays eager.
@@ -25,7 +27,7 @@ import test_gpu_kvfault as KV  # noqa: E402
 import test_gpu_kvtrials as KT  # noqa: E402
 from guarded import POISONS  # noqa: E402
 from test_gpu_beam import assert_same, gpu_beam  # noqa: E402
-from test_gpu_bounds import Guards, _skinny_ref, _skinny_run, assert_ok, np_  # noqa: E402
+from test_gpu_bounds import GB_PARAMS, _skinny_ref, _skinny_run, assert_ok, gb, np_  # noqa: E402,F401
 from test_gpu_dfault_cached import cached, check_scored  # noqa: E402
 from test_gpu_long_fused import stats  # noqa: E402
 from test_gpu_model_configs import GR_L, greedy_case  # noqa: E402
@@ -40,18 +42,18 @@ L = 8     # the fault drivers' max_len
 # =====================================================================================
 # 1. FFN2 per op
 # =====================================================================================
-def ffn2_ref(amode, M, K, oracle_model):
+def ffn2_ref(amode, M, K, oracle_model, N=512):
     """_skinny_ref's case with two sets of values planted.  x: the absmax of even rows at column
     0, of odd rows at column K - 1 (a half-row maximum that misses the other half changes the
     scale; the all-zero last row stays).  W: row n carries code 1 + (n + 5 s) % 127 — nonzero,
     different for every k-step s of the row — in the last 16 columns of each 64-column k-step
     (a k-step dealt to no wave, or to two, changes the sum)."""
-    r = dict(_skinny_ref(amode, M, 512, K, 8, oracle_model))
+    r = dict(_skinny_ref(amode, M, N, K, 8, oracle_model))
     x, qw = r["x"].copy(), r["qw"].copy()
     top = 2 * np.abs(x).max(-1)
     x[0::2, 0], x[1::2, K - 1] = top[0::2], -top[1::2]
-    n, s = np.arange(512)[:, None, None], np.arange(K // 64)[None, :, None]
-    qw.reshape(512, K // 64, 64)[:, :, 48:] = 1 + (n + 5 * s) % 127
+    n, s = np.arange(N)[:, None, None], np.arange(K // 64)[None, :, None]
+    qw.reshape(N, K // 64, 64)[:, :, 48:] = 1 + (n + 5 * s) % 127
     r["x"], r["qw"] = x, qw
     r["qx"], r["sx"] = O.quant_rows(x)
     if amode == 2:
@@ -60,30 +62,60 @@ def ffn2_ref(amode, M, K, oracle_model):
     return r
 
 
-@pytest.mark.parametrize("M", [1, 5, 33, 97])
-@pytest.mark.parametrize("amode", [3, 2, 0])
-@pytest.mark.parametrize("K", KS)
-def test_ffn2(torch, oracle_model, K, amode, M):
-    gb = Guards(torch, POISONS[0])
-    r = ffn2_ref(amode, M, K, oracle_model)
-    rc, out, pm = _skinny_run(gb, r, amode, M, 512, K, 8, 2)
+def _gb_cases(cases):
+    """(argvalues, ids) of `cases` under each parameter of test_gpu_bounds.py's gb fixture (both
+    poisons at 256-byte alignment, 16 (mod 256) under the first).  The first parameter is what
+    these tests ran with before they took the fixture, and keeps their ids."""
+    vals, ids = [], []
+    for (poison, skew), gid in zip(GB_PARAMS, ("", "poison5A-", "align16-poisonA5-")):
+        assert (poison, skew) == {"": (POISONS[0], 0), "poison5A-": (POISONS[1], 0),
+                                  "align16-poisonA5-": (POISONS[0], 16)}[gid]
+        for c, cid in cases:
+            vals.append(((poison, skew),) + tuple(c))
+            ids.append(gid + cid)
+    return vals, ids
+
+
+# the full M x amode x K product with the step's epilogue (residual, N = 512); no epilogue flag
+# (k_skinny<.., 0> at every M: the 8-wave kernel takes the residual form only) and N = 48 (three
+# column blocks) at the narrowest K, an odd K / 256 and the widest K
+FFN2_CASES = [((K, amode, M, 2, 512), "%d-%d-%d" % (K, amode, M))
+              for K in KS for amode in (3, 2, 0) for M in (1, 5, 33, 97)]
+FFN2_CASES += [((K, amode, M, flags, N), "%d-%d-%d-flags%d-N%d" % (K, amode, M, flags, N))
+               for flags, N in ((0, 512), (0, 48), (2, 48)) for K in (256, 768, 1792)
+               for amode in (3, 2, 0) for M in (1, 5, 33, 97)]
+_FFN2 = _gb_cases(FFN2_CASES)
+
+
+@pytest.mark.parametrize("gb,K,amode,M,flags,N", _FFN2[0], ids=_FFN2[1], indirect=["gb"])
+def test_ffn2(gb, oracle_model, K, amode, M, flags, N):
+    """Every case at both alignments and under both poisons (the gb fixture).  flags 0: the
+    residual is still passed and must not reach the result."""
+    r = ffn2_ref(amode, M, K, oracle_model, N)
+    rc, out, pm = _skinny_run(gb, r, amode, M, N, K, 8, flags)
     assert_ok(rc, "qtx_skinny_linear")
     gb.check()
-    y = r["res"] + O.linear_epilogue(r["acc"], r["sx"], r["sw"], r["b"], relu=False)
+    y = O.linear_epilogue(r["acc"], r["sx"], r["sw"], r["b"], relu=False)
+    if flags & 2:
+        y = r["res"] + y
     np.testing.assert_array_equal(np_(out), y)
     gb.assert_poison(pm, "pmax_out")
 
 
-@pytest.mark.parametrize("amode,bits,flags", [(1, 8, 2), (3, 4, 2), (3, 8, 1), (0, 8, 5)])
-def test_ffn2_refusals(torch, oracle_model, amode, bits, flags):
+_REFUSALS = _gb_cases([((amode, bits, flags), "%d-%d-%d" % (amode, bits, flags))
+                       for amode, bits, flags in [(1, 8, 2), (3, 4, 2), (3, 8, 1), (0, 8, 5)]])
+
+
+@pytest.mark.parametrize("gb,amode,bits,flags", _REFUSALS[0], ids=_REFUSALS[1], indirect=["gb"])
+def test_ffn2_refusals(gb, oracle_model, amode, bits, flags):
     """What include/qtx.h excludes at the new K: the LayerNorm prologue, 4-bit weights, the ReLU
     and row-maximum epilogues — QTX_E_UNSUPPORTED, nothing written."""
-    gb = Guards(torch, POISONS[0])
     r = dict(_skinny_ref(3, 5, 512, 768, 8, oracle_model))
     rc, out, pm = _skinny_run(gb, r, amode, 5, 512, 768, bits, flags)
     assert rc == 4
     gb.check()
     gb.assert_poison(out, "out")
+    gb.assert_poison(pm, "pmax_out")
 
 
 # =====================================================================================

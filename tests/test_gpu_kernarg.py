@@ -65,6 +65,12 @@ CASES = [(a, N, K, fl, 8, alias) for a, N, K in SHAPES for fl in FLAGS
          for alias in ((False, True) if fl & 2 else (False,))]
 # 4-bit weights (k_skinny / k_skinny_wide only; K = 2048 then runs k_skinny with every prologue)
 CASES += [(a, N, K, fl, 4, fl == 2) for a, N, K in SHAPES for fl in (2, 5)]
+# the FFN2 widths of csrc/qtx_decode_dff.hip (narrowest, an odd K / 256, widest): what
+# include/qtx.h accepts there — 8-bit weights, no flag or the residual.  With the residual and
+# amode 2 / 3: k_skinny8_dff<Q, false / true>; else k_skinny at the new K
+SHAPES_DFF = [(a, 512, K) for K in (256, 768, 1792) for a in (0, 2, 3)]
+CASES += [(a, N, K, fl, 8, alias) for a, N, K in SHAPES_DFF for fl in (0, 2)
+          for alias in ((False, True) if fl & 2 else (False,))]
 
 
 def _skinny_case(torch, M, amode, N, K, flags, bits, alias):

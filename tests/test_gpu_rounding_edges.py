@@ -93,6 +93,50 @@ def test_skinny_prologue(torch, amode, K, nparts, M, start):
                                   res + O.linear_epilogue(O.int_gemm(qx, qw), sx, sw, b))
 
 
+def _skinny_residual(torch, amode, K, nparts, h, seed):
+    """qtx_skinny_linear (N = 512, residual, in place) on the fp32 rows h with random int8 W:
+    (the kernel's result, the oracle's)."""
+    rng = np.random.default_rng(seed)
+    M = len(h)
+    qw, sw, b = E.rand_weights(rng, 512, K)
+    res = rng.standard_normal((M, 512)).astype(f32)
+    out = dev(torch, res.copy())
+    parts = S0
+    if amode == 2:
+        parts = P(dev(torch, np.abs(h).reshape(M, nparts, K // nparts).max(-1).T.copy()))
+    call("qtx_skinny_linear", amode, S0, S0, P(dev(torch, h)), K, S0, S0, parts, nparts,
+         P(dev(torch, qw)), P(dev(torch, sw)), P(dev(torch, b)), M, 512, K, 8, 2,
+         P(out), P(out), S0, S0)
+    qx, sx = O.quant_rows(h)
+    return out.cpu().numpy(), res + O.linear_epilogue(O.int_gemm(qx, qw), sx, sw, b)
+
+
+@pytest.mark.parametrize("amode,K,nparts,M,start", E.SKINNY_DFF)
+def test_skinny_dff_prologue(torch, amode, K, nparts, M, start):
+    """test_skinny_prologue at the FFN2 widths of csrc/qtx_decode_dff.hip, K = 256 .. 1792:
+    M = 3 runs k_skinny8_dff (two waves per row, each with its own near-tie vote; float2
+    loads and a padded pack for odd K / 256), 40 k_skinny's 4-row blocks, 100 its 8-row
+    blocks; amode 2 with the step's K / 16 partial maxima and with the 8-wave kernel's 128."""
+    h, _ = E.direct_rows(K, M, start)
+    got, want = _skinny_residual(torch, amode, K, nparts, h, 1000 * amode + K + nparts + M)
+    np.testing.assert_array_equal(got, want)
+
+
+@pytest.mark.parametrize("amode", [3, 2])
+@pytest.mark.parametrize("K", E.DFF_KS)
+def test_skinny8_dff_lone_rows(torch, K, amode):
+    """Every row of E.lone_rows_dff8(K) through k_skinny8_dff (M <= 32: one to three calls): one
+    near-tie per row, in either half, every load and element of a lane, lanes 0 and 63 (the CPU
+    test states the coverage) — the half's wave vote must see it, and the other half's wave must
+    get its codes right without one."""
+    rows = E.lone_rows_dff8(K)[0]
+    for i, h in enumerate(np.array_split(rows, -(-len(rows) // 32))):
+        assert len(h) <= 32
+        got, want = _skinny_residual(torch, amode, K, K // 16 if amode == 2 else 0, h,
+                                     7000 * amode + K + i)
+        np.testing.assert_array_equal(got, want)
+
+
 @pytest.mark.parametrize("lone", [False, True])
 def test_decode_self_attention(torch, lone):
     """quant_one on the step's q | k | v thirds (three mantissas per sentence; tie rows, or

@@ -23,6 +23,7 @@ import rounding_edges as E  # noqa: E402
 
 f32 = np.float32
 WIDTHS = (256, 512, 768, 2048)
+DFF_WIDTHS = (1024, 1280, 1536, 1792)      # with 256 and 768: E.DFF_KS (csrc/qtx_decode_dff.hip)
 
 
 def check_rows(x, n_bits=8, relu=False, c_min=16):
@@ -35,7 +36,7 @@ def check_rows(x, n_bits=8, relu=False, c_min=16):
 
 
 @pytest.mark.parametrize("qmax,bits", [(127.0, 8), (7.0, 4)])
-@pytest.mark.parametrize("D", WIDTHS)
+@pytest.mark.parametrize("D", WIDTHS + DFF_WIDTHS)
 def test_tie_rows_exact(D, qmax, bits):
     """In rational arithmetic every tie element has x / s == k + 1/2 and the oracle gives the
     even neighbour and the scale s exactly; every k, and every neighbour of its tie, is in
@@ -60,7 +61,7 @@ def test_tie_rows_exact(D, qmax, bits):
 
 
 @pytest.mark.parametrize("qmax,bits", [(127.0, 8), (7.0, 4)])
-@pytest.mark.parametrize("D", WIDTHS)
+@pytest.mark.parametrize("D", WIDTHS + DFF_WIDTHS)
 def test_tie_rows_discriminate(D, qmax, bits):
     for mant, exp in (E.COMBOS if bits == 8 else E.COMBOS_Q7):
         cnt = check_rows(E.tie_rows(D, mant, exp, qmax), bits)
@@ -75,7 +76,7 @@ def check_lone(x, relu=False):
     assert (worst == 1).all(), worst
 
 
-@pytest.mark.parametrize("D", WIDTHS)
+@pytest.mark.parametrize("D", WIDTHS + DFF_WIDTHS)
 def test_lone_rows(D):
     """A lone row: every element but one is an exact integer multiple of the scale (rational
     arithmetic), the one is positive, its row's model gets exactly its code wrong and no model
@@ -99,6 +100,63 @@ def test_lone_rows(D):
     check_lone(x)
 
 
+@pytest.mark.parametrize("K", E.DFF_KS)
+def test_lone_rows_dff8(K):
+    """The lone rows tests/test_gpu_rounding_edges.py::test_skinny8_dff_lone_rows sends to
+    k_skinny8_dff, in that kernel's layout (E.dff8_slot): the near-ties visit both halves of
+    the row, every (load, element) of either half — for odd K / 256 the last load among them,
+    whose two codes share a dword with the zero fillers — lane 0 and lane 63 of either half and
+    lanes between them.  Every row, the added ones included, has the exact scale of
+    its set, one element that is no integer multiple of it, and exactly that code wrong under
+    its own model.
+    Rows (of which added to lone_rows(K)) at K = 256 .. 1792: 18 (6), 41 (5), 50 (2), 63 (3),
+    74 (2), 87 (3): one to three calls of at most 32 rows."""
+    x, cols, models = E.lone_rows_dff8(K)
+    base = E.lone_rows(K)
+    n = len(base[0])
+    np.testing.assert_array_equal(x[:n], base[0])
+    assert cols[:n].tolist() == base[1].tolist() and models[:n] == base[2]
+    assert len(x) == len(cols) == len(models) and -(-len(x) // 32) <= 3
+    Q = K // 256
+    vw, nc = (4, Q // 2) if Q % 2 == 0 else (2, Q)
+    slots = [E.dff8_slot(K, c) for c in cols]
+    assert all(E.dff8_col(K, *s) == c for s, c in zip(slots, cols))
+    assert {(h, c, e) for h, c, _, e in slots} == {(h, c, e) for h in range(2) for c in range(nc)
+                                                   for e in range(vw)}
+    for h in range(2):
+        lanes = {s[2] for s in slots if s[0] == h}
+        assert {0, 63} <= lanes and lanes - {0, 63}, (h, sorted(lanes))
+    if Q % 2:
+        assert {(h, e) for h, c, _, e in slots if c == Q - 1} == {(h, e) for h in range(2)
+                                                                  for e in range(2)}
+    (q, s), cnt = E.discrimination(x)
+    ref = q.astype(np.float64)
+    for i, (row, col, model) in enumerate(zip(x, cols, models)):
+        mant, exp = E.COMBOS[i % len(E.COMBOS)]
+        assert s[i] == E.scale_of(mant, exp) and model == E.LONE_MODELS[i % 3][0]
+        fs = Fraction(float(s[i]))
+        whole = np.array([(Fraction(float(v)) / fs).denominator == 1 for v in row])
+        assert not whole[col] and whole.sum() == K - 1 and row[col] > 0
+        bad = np.flatnonzero(E.model_recip(row[None], s[i:i + 1], dict(E.LONE_MODELS)[model])[0] != ref[i])
+        assert bad.tolist() == [col]
+    check_lone(x)
+
+
+def test_skinny_dff_rows():
+    """The rows of the FFN2 prologue cases at the widths of csrc/qtx_decode_dff.hip
+    (E.SKINNY_DFF): every tie row meets check_rows' bounds, every lone row check_lone's, and
+    the scales are the sets' exact ones."""
+    assert {c[1] for c in E.SKINNY_DFF} == set(E.DFF_KS) and len(E.SKINNY_DFF) == 54
+    for amode, K, nparts, M, start in E.SKINNY_DFF:
+        assert K % nparts == 0 if amode == 2 else nparts == 0
+        h, lone = E.direct_rows(K, M, start)
+        check_rows(h[~lone])
+        check_lone(h[lone])
+        _, s = O.quant_rows(h)
+        ok = {float(E.scale_of(m, e)) for m, e in E.COMBOS}
+        assert set(s.tolist()) <= ok
+
+
 def test_rejected_mantissas():
     """Why 5, 9, 17 (and 3) are not used: model (a) gets (almost) every code right."""
     for mant, most in ((5, 0), (9, 0), (17, 0), (3, 99)):
@@ -109,7 +167,7 @@ def test_rejected_mantissas():
 def test_direct_rows():
     """The rows the direct-input cases use (qtx_row_quant, the skinny amode 2 / 3 prologues,
     the decode attention's q | k | v thirds)."""
-    for D in WIDTHS:
+    for D in WIDTHS + DFF_WIDTHS:
         check_rows(E.all_rows(D))
         check_rows(E.all_rows(D, 7.0), 4)
     for K, M, start in [c[1:2] + c[3:] for c in E.SKINNY_DIRECT] + [E.DECODE_CROSS_Q]:
