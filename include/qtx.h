@@ -73,7 +73,10 @@ typedef enum {
 typedef struct qtx_model qtx_model;
 
 /* make_model hyper-parameters (model.py:15-16).  d_model must be 512, d_ff a multiple of
- * 256 up to 2048, n_heads * 64 == d_model.  weight_bits: 8 (W8A8) or 4 (packed int4).
+ * 256 up to 2048, n_heads 4, 8 or 16 (head widths 128, 64, 32; with 4 or 16 heads every
+ * entry that injects a fault, and every other entry given a non-NULL fault or n_faults > 0,
+ * returns QTX_E_UNSUPPORTED before it writes anything; the per-op attention entries for those
+ * widths: qtx_heads.h).  weight_bits: 8 (W8A8) or 4 (packed int4).
  * Every config qtx_model_create accepts runs every model-level call (tests/
  * test_gpu_model_configs.py; the kernel chain per config: DESIGN.md, supported shapes):
  * the row-GEMM encoder / decoder chain needs d_ff % 512 == 0, the fused decode step

@@ -158,14 +158,14 @@ int row_ffn1(const qtx_config& c, const QLin& L, const int8_t* a8, const float* 
   return QTX_OK;
 }
 
-AttnArgs attn_args(const Scratch& s, int B, int Sq, int Sk, long kbs_rows) {
+AttnArgs attn_args(const Scratch& s, int B, int Sq, int Sk, long kbs_rows, int H) {
   AttnArgs a{};
   const int D = 512;
   a.q = s.q8; a.q_bs = (long)Sq * D; a.q_ld = D; a.sq = s.sq; a.sq_bs = Sq;
   a.k = s.k8; a.k_bs = kbs_rows * D; a.k_ld = D; a.sk = s.sk; a.sk_bs = kbs_rows;
   a.v = s.v8; a.v_bs = kbs_rows * D; a.v_ld = D; a.sv = s.sv; a.sv_bs = kbs_rows;
   a.ctx = s.ctx; a.c_bs = (long)Sq * D; a.c_ld = D;
-  a.B = B; a.H = 8; a.Sq = Sq; a.Sk = Sk;
+  a.B = B; a.H = H; a.dk = D / H; a.Sq = Sq; a.Sk = Sk;
   return a;
 }
 
@@ -184,7 +184,7 @@ int self_attn_block(const qtx_config& c, const QLin& qkv, const QLin& o,
   RC(quant(s.y, 3 * D, M, D, s.q8, s.sq, st));
   RC(quant(s.y + D, 3 * D, M, D, s.k8, s.sk, st));
   RC(quant(s.y + 2 * D, 3 * D, M, D, s.v8, s.sv, st));
-  AttnArgs a = attn_args(s, B, S, S, S);
+  AttnArgs a = attn_args(s, B, S, S, S, c.n_heads);
   a.mask = mask; a.m_bs = m_bs; a.m_is = m_is;
   a.dec = dec;
   HIPCHK(launch_attention(a, st));
@@ -411,7 +411,7 @@ int encoder_run(const qtx_model* m, const float* x, const uint8_t* mask, int B, 
     RC(row_quant(L.qkv, s.a8, s.sa, M, s.q8, s.sq, st, fa(G_QKV), kp,
                  zero_ffn1 ? s.y : nullptr, zero_ffn1 ? ffn1_scratch16(M) : 0));
     if (l == 0 && after_first) HIPCHK(hipEventRecord(after_first, st));
-    AttnArgs a = attn_args(s, B, S, S, S);
+    AttnArgs a = attn_args(s, B, S, S, S, c.n_heads);
     a.mask = mask; a.m_bs = S; a.m_is = 0;
     a.c_ld = D;
     AttnFault af;
@@ -510,7 +510,7 @@ int cross_attn_block(const qtx_model* m, const DecLayer& L, int l, Scratch& s,
   RC(ln_quant(s.x, M, L.ln[1], D, s.a8, s.sa, st));
   RC(linear(c, L.cq, s.a8, s.sa, M, 0, nullptr, s.y, D, st, fcq));
   RC(quant(s.y, D, M, D, s.q8, s.sq, st));
-  AttnArgs a = attn_args(s, B, T, S, S);
+  AttnArgs a = attn_args(s, B, T, S, S, c.n_heads);
   a.k = x.k8[l]; a.sk = x.sk[l]; a.v = x.v8[l]; a.sv = x.sv[l];
   a.mask = src_mask; a.m_bs = S; a.m_is = 0;
   a.dec = 1;
@@ -569,18 +569,18 @@ SkinnyArgs skinny(int wbits, const QLin& L, int M, int amode, int flags, float* 
   return s;
 }
 
-DecAttnArgs dec_attn_self(const GreedyWS& g, int l, int B, int max_len, int host_step1) {
+DecAttnArgs dec_attn_self(const GreedyWS& g, int l, int B, int max_len, int host_step1, int H) {
   DecAttnArgs at{};
   at.y = g.dec.y; at.ldy = 3 * 512; at.kv_new = 1; at.step = g.step;
   at.kc = g.kc[l]; at.vc = g.vc[l]; at.skc = g.skc[l]; at.svc = g.svc[l]; at.kv_bs = max_len;
-  at.ctx = g.dec.ctx; at.B = B; at.host_step1 = host_step1;
+  at.ctx = g.dec.ctx; at.B = B; at.host_step1 = host_step1; at.dk = 512 / H;
   return at;
 }
-DecAttnArgs dec_attn_cross(const GreedyWS& g, int l, int B, int S, const uint8_t* src_mask) {
+DecAttnArgs dec_attn_cross(const GreedyWS& g, int l, int B, int S, const uint8_t* src_mask, int H) {
   DecAttnArgs at{};
   at.y = g.dec.y; at.ldy = 512; at.kv_new = 0; at.S = S; at.mask = src_mask;
   at.kc = g.cross.k8[l]; at.vc = g.cvg[l]; at.skc = g.cross.sk[l]; at.svc = g.cross.sv[l];
-  at.kv_bs = S; at.ctx = g.dec.ctx; at.B = B;
+  at.kv_bs = S; at.ctx = g.dec.ctx; at.B = B; at.dk = 512 / H;
   return at;
 }
 
@@ -687,7 +687,7 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
     } else {
       RC(ln_linear(L.qkv, L.ln[0], 0, s.y, 3 * D, 2));
     }
-    DecAttnArgs at = dec_attn_self(g, l, B, max_len, host_pos ? t_host + 1 : 0);
+    DecAttnArgs at = dec_attn_self(g, l, B, max_len, host_pos ? t_host + 1 : 0, c.n_heads);
     at.pmax = own_max ? nullptr : g.pmax_a;
     if (g.beam && g.beam->ancestry)   // cached rows through the ancestry table (no reorder)
       QTX_RUN(4, launch_dec_attn_beam(at, g.beam->anc, g.beam->K, B, st));
@@ -697,7 +697,7 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
     a.X = s.ctx; a.ldx = D; a.pmax_in = g.pmax_a; a.pmax_n = 8; a.res = s.x; a.ldr = D;
     QTX_RUN(16, launch_skinny(a, wb, st));
     RC(ln_linear(L.cq, L.ln[1], 0, s.y, D, 2));
-    at = dec_attn_cross(g, l, B, S, src_mask);
+    at = dec_attn_cross(g, l, B, S, src_mask, c.n_heads);
     at.pmax = own_max ? nullptr : g.pmax_a;
     QTX_RUN(8, launch_dec_attn(at, B, st));
     a = skinny(wb, L.co, B, own_max ? A_F32R : A_F32Q, EPI_RESIDUAL, s.x, D);
@@ -757,7 +757,7 @@ int greedy_step_fused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len
 }
 
 int cached_self_attn_unfused(GreedyWS& g, int l, int B, int max_len, int t, const AttnFault* af,
-                             hipStream_t st) {
+                             hipStream_t st, int H) {
   const int D = 512;
   Scratch& s = g.dec;
   RC(quant(s.y, 3 * D, B, D, s.q8, s.sq, st));
@@ -768,7 +768,7 @@ int cached_self_attn_unfused(GreedyWS& g, int l, int B, int max_len, int t, cons
   else kr.dst_off_dev = vr.dst_off_dev = g.step;
   HIPCHK(launch_rows(kr, st));
   HIPCHK(launch_rows(vr, st));
-  AttnArgs a = attn_args(s, B, 1, t >= 0 ? t + 1 : 0, max_len);
+  AttnArgs a = attn_args(s, B, 1, t >= 0 ? t + 1 : 0, max_len, H);
   a.k = g.kc[l]; a.sk = g.skc[l]; a.v = g.vc[l]; a.sv = g.svc[l];
   if (t < 0) { a.sk_dev = g.step; a.sk_add = 1; }
   a.dec = 1;
@@ -790,7 +790,7 @@ int greedy_step_unfused(const qtx_model* m, GreedyWS& g, int B, int S, int max_l
     const DecLayer& L = m->dec[l];
     RC(ln_quant(s.x, B, L.ln[0], D, s.a8, s.sa, st));
     RC(linear(c, L.qkv, s.a8, s.sa, B, 0, nullptr, s.y, 3 * D, st));
-    RC(cached_self_attn_unfused(g, l, B, max_len, -1, nullptr, st));
+    RC(cached_self_attn_unfused(g, l, B, max_len, -1, nullptr, st, c.n_heads));
     RC(quant(s.ctx, D, B, D, s.a8, s.sa, st));
     RC(linear(c, L.o, s.a8, s.sa, B, EPI_RESIDUAL, s.x, s.x, D, st));
     RC(cross_attn_block(m, L, l, s, g.cross, B, 1, S, src_mask, st));
@@ -841,7 +841,7 @@ int decoder_body(const qtx_model* m, Scratch& s, const CrossKV& x, const uint8_t
     const DecLayer& L = m->dec[l];
     auto fa = [&](GemmId gid) { return fault_for(f, 1, l, gid, M, c); };
     RC(row_quant(L.qkv, s.a8, s.sa, M, s.q8, s.sq, st, fa(G_QKV)));
-    AttnArgs a = attn_args(s, B, T, T, T);
+    AttnArgs a = attn_args(s, B, T, T, T, c.n_heads);
     a.mask = tgt_mask; a.m_bs = tm_bs; a.m_is = T;
     a.c_ld = D;
     a.dec = 1;
@@ -849,7 +849,7 @@ int decoder_body(const qtx_model* m, Scratch& s, const CrossKV& x, const uint8_t
     RC(attention_quant(a, attn_fault_for(f, 1, l, false, T, T, af) ? &af : nullptr, M, D, s, false, st));
     RC(row_res_ln(L.o, s.a8, s.sa, M, s.x, L.ln[1], s.a8, s.sa, nullptr, st, fa(G_O)));
     RC(row_quant(L.cq, s.a8, s.sa, M, s.q8, s.sq, st, fa(G_CQ)));
-    a = attn_args(s, B, T, S, S);
+    a = attn_args(s, B, T, S, S, c.n_heads);
     a.k = x.k8[l]; a.sk = x.sk[l]; a.v = x.v8[l]; a.sv = x.sv[l];
     a.mask = src_mask; a.m_bs = S; a.m_is = 0;
     a.dec = 1;
@@ -1013,6 +1013,7 @@ int32_t qtx_encoder_forward_fault(const qtx_model* m, const float* x, const uint
   if (!m || !x || !src_mask || !out || !ws) return fail(QTX_E_INVALID, "null argument");
   if (B <= 0 || S <= 0 || S > 512) return fail(QTX_E_INVALID, "bad shape B=%d S=%d", B, S);
   RC(check_workspace(ws_bytes, enc_ws(m->cfg, B, S)));
+  RC(check_fault_heads(m->cfg, f != nullptr));
   RC(check_fault(m, f, 0, B, S, 0));
   hipStream_t st = (hipStream_t)stream;
   CallFrame fr;
@@ -1069,6 +1070,7 @@ int32_t qtx_decoder_forward_fault(const qtx_model* m, const float* y, const floa
   if (bad_decode_shape(m->cfg, B, S, T))
     return fail(QTX_E_INVALID, "bad shape B=%d T=%d S=%d (table %d)", B, T, S, m->cfg.max_len);
   RC(check_workspace(ws_bytes, dec_ws(m->cfg, B, T, S)));
+  RC(check_fault_heads(m->cfg, f != nullptr));
   RC(check_fault(m, f, 1, B, T, S));
   hipStream_t st = (hipStream_t)stream;
   const qtx_config& c = m->cfg;
@@ -1105,6 +1107,7 @@ static int32_t greedy_decode(const qtx_model* m, const int64_t* src, const uint8
   if (scored) RC(refuse_dbg_tail("scored decode"));
   const Groups gr = decode_groups(B);
   RC(check_workspace(ws_bytes, greedy_ws(c, gr, B, S, max_len, scored)));
+  RC(check_fault_heads(c, f != nullptr));
   if (f && f->kind != QTX_FAULT_NONE && f->module != 0)
     return fail(QTX_E_UNSUPPORTED, "greedy decode takes encoder faults (decoder faults: "
                                    "qtx_decoder_forward_fault on the step's prefix)");

@@ -753,13 +753,16 @@ hipError_t launch_dec_attn(const DecAttnArgs& a, int B, hipStream_t st) {
   if (a.ldy < 0 || a.ldy >= (1L << 31) || a.kv_bs >= (1L << 31)) return hipErrorInvalidValue;   // 32-bit in the lead block
   // up to DEC_MAXK rows to load: one wave per (sentence, head), the keys in its registers;
   // up to DEC_LONG_MAXK: four waves (k_dec_attn_long, qtx_decode_long.hip)
+  if (a.dk != 32 && a.dk != 64 && a.dk != 128) return hipErrorInvalidValue;
   if (a.kv_new) {
     if (a.kv_bs <= 0 || a.kv_bs > DEC_LONG_MAXK || a.host_step1 < 0 || a.host_step1 > a.kv_bs)
       return hipErrorInvalidValue;
+    if (a.dk != 64) return launch_dec_attn_hd(a, B, st);   // head widths 32 / 128: every key count
     const int nrows = a.host_step1 > 0 ? a.host_step1 : (int)a.kv_bs;
     return nrows <= DEC_MAXK ? dec_attn_nit<true>(a, B, nrows, st) : launch_dec_attn_long(a, B, st);
   }
   if (a.S <= 0 || a.S > DEC_LONG_MAXK) return hipErrorInvalidValue;
+  if (a.dk != 64) return launch_dec_attn_hd(a, B, st);
   return a.S <= DEC_MAXK ? dec_attn_nit<false>(a, B, a.S, st) : launch_dec_attn_long(a, B, st);
 }
 

@@ -74,7 +74,7 @@ int enctrials_encoder(const qtx_model* m, const uint8_t* mask, int B, int S, flo
   if (rows) RC(ln_quant(s.x, M, m->enc[0].ln[0], D, s.a8, s.sa, st));
   for (int l = 0; l < NL; ++l) {
     const EncLayer& L = m->enc[l];
-    AttnArgs a = attn_args(s, B, S, S, S);
+    AttnArgs a = attn_args(s, B, S, S, S, c.n_heads);
     a.mask = mask; a.m_bs = S; a.m_is = 0;
     a.c_ld = D;
     // the golden attention, then the affected (sentence, head) rows of each attention trial
@@ -202,6 +202,7 @@ int32_t qtx_greedy_decode_enctrials(const qtx_model* m, const int64_t* src, cons
   RC(check_top2_vocab(c));
   const Groups gr = decode_groups(B);
   RC(check_workspace(ws_bytes, enctrials_ws(c, gr, B, S, max_len)));
+  RC(check_fault_heads(c, true));
   TrialPlan plan;
   plan.hits.assign((size_t)c.n_layers, std::vector<int>(G_CO + 1, 0));
   plan.attn.resize((size_t)c.n_layers);

@@ -134,6 +134,7 @@ int32_t qtx_greedy_decode_dfault(const qtx_model* m, const int64_t* src, const u
   if (scored || rec_ids) RC(check_top2_vocab(c));
   const Groups gr = decode_groups(B);
   RC(check_workspace(ws_bytes, dfault_ws(c, gr, B, S, max_len)));
+  RC(check_fault_heads(c, true));
   const int last = max_len - 1;             // steps 0 .. last-1
   const bool applied = fault_step < last;   // else the fault's step is never run: golden
   if (applied) RC(check_fault(m, f, 1, B, fault_step + 1, S));
@@ -190,6 +191,7 @@ int32_t qtx_greedy_dfault_resume(const qtx_model* m, int32_t B, int32_t S, int32
   RC(check_top2_vocab(c));
   const Groups gr = decode_groups(B);
   RC(check_workspace(ws_bytes, dfault_ws(c, gr, B, S, max_len)));
+  RC(check_fault_heads(c, true));
   qtx_model::DfaultHdr h{};
   {
     qtx_model* mm = const_cast<qtx_model*>(m);
@@ -345,17 +347,17 @@ int kvfault_step(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, int
     RC(ln_quant(s.x, B, L.ln[0], D, s.a8, s.sa, st));
     RC(linear(c, L.qkv, s.a8, s.sa, B, 0, nullptr, s.y, 3 * D, st, fa(G_QKV)));
     if (fused) {
-      HIPCHK(launch_dec_attn(dec_attn_self(g, l, B, max_len, t + 1), B, st));
+      HIPCHK(launch_dec_attn(dec_attn_self(g, l, B, max_len, t + 1, c.n_heads), B, st));
       if (self_f) RC(fused_attn_fault(af_self, l, false));
     } else {
-      RC(cached_self_attn_unfused(g, l, B, max_len, t, self_f ? &af_self : nullptr, st));
+      RC(cached_self_attn_unfused(g, l, B, max_len, t, self_f ? &af_self : nullptr, st, c.n_heads));
     }
     RC(quant(s.ctx, D, B, D, s.a8, s.sa, st));
     RC(linear(c, L.o, s.a8, s.sa, B, EPI_RESIDUAL, s.x, s.x, D, st, fa(G_O)));
     if (fused) {
       RC(ln_quant(s.x, B, L.ln[1], D, s.a8, s.sa, st));
       RC(linear(c, L.cq, s.a8, s.sa, B, 0, nullptr, s.y, D, st, fa(G_CQ)));
-      HIPCHK(launch_dec_attn(dec_attn_cross(g, l, B, S, g.mask), B, st));
+      HIPCHK(launch_dec_attn(dec_attn_cross(g, l, B, S, g.mask, c.n_heads), B, st));
       if (cross_f) RC(fused_attn_fault(af_cross, l, true));
       RC(quant(s.ctx, D, B, D, s.a8, s.sa, st));
       RC(linear(c, L.co, s.a8, s.sa, B, EPI_RESIDUAL, s.x, s.x, D, st, fa(G_CO)));
@@ -402,6 +404,7 @@ int32_t qtx_greedy_decode_kvfault(const qtx_model* m, const int64_t* src, const 
   if (scored || rec_ids) RC(check_top2_vocab(c));
   const Groups gr = decode_groups(B);
   RC(check_workspace(ws_bytes, kvfault_ws(c, gr, B, S, max_len)));
+  RC(check_fault_heads(c, true));
   const int last = max_len - 1;          // steps 0 .. last-1
   const bool applied = step < last;      // else nothing runs at or after `step`: golden
   const bool fused = greedy_fused(c, S, max_len);

@@ -182,6 +182,15 @@ inline int refuse_dbg_tail(const char* entry) {
 inline int check_fault_bits(const qtx_config& c) {
   return c.weight_bits != 8 ? fail(QTX_E_UNSUPPORTED, "fault injection needs 8-bit weights") : QTX_OK;
 }
+// Models with 4 or 16 heads (head widths 128 / 32): the oracle defines no fault for them
+// (its fault paths divide by 8 and split columns by 64), so every fault entry refuses them
+// before anything is launched or written.  have_fault: whether the call carries a fault (the
+// entries that exist only to inject one pass true).
+inline int check_fault_heads(const qtx_config& c, bool have_fault) {
+  return have_fault && c.n_heads != 8
+             ? fail(QTX_E_UNSUPPORTED, "fault injection needs 8 heads (n_heads %d)", c.n_heads)
+             : QTX_OK;
+}
 inline int check_workspace(size_t ws_bytes, size_t need) {
   return ws_bytes < need ? fail(QTX_E_WORKSPACE, "workspace too small") : QTX_OK;
 }
@@ -249,14 +258,14 @@ Groups decode_groups(int B);
 bool greedy_fused(const qtx_config& c, int S, int max_len);   // the fused step, else the unfused
 bool greedy_fused_long(const qtx_config& c, int S, int max_len);   // plain / scored greedy: to 512 keys
 // k_dec_attn's arguments for layer l's cached self / cross attention on g's step scratch
-DecAttnArgs dec_attn_self(const GreedyWS& g, int l, int B, int max_len, int host_step1);
-DecAttnArgs dec_attn_cross(const GreedyWS& g, int l, int B, int S, const uint8_t* src_mask);
+DecAttnArgs dec_attn_self(const GreedyWS& g, int l, int B, int max_len, int host_step1, int H);
+DecAttnArgs dec_attn_cross(const GreedyWS& g, int l, int B, int S, const uint8_t* src_mask, int H);
 // The unfused step's cached self-attention of layer l: q, and the K and V rows into the cache
 // at the step's position, quantized from the Q/K/V GEMM's output in s.y; attention over
 // position + 1 keys (af: its faulty row recomputed).  t >= 0: the position from the host,
 // else the device counter g.step.
 int cached_self_attn_unfused(GreedyWS& g, int l, int B, int max_len, int t, const AttnFault* af,
-                             hipStream_t st);
+                             hipStream_t st, int H);
 int greedy_step_unfused(const qtx_model* m, GreedyWS& g, int B, int S, int max_len,
                         int64_t* ids, const uint8_t* src_mask, hipStream_t st);
 // x's values of every layer in k_dec_attn's 4-key groups (cvg: all layers, GreedyWS::cvg[0])
@@ -281,8 +290,9 @@ StepRequest step_request(const qtx_model* m, std::vector<GreedyWS>& gv, const Gr
 // steps per graph of the decodes that run in chunks (QTX_GRAPH_STEPS, default 8)
 inline int graph_chunk() { return knobs().graph_steps > 0 ? knobs().graph_steps : 8; }
 int run_steps(const qtx_model* m, const StepRequest& rq, hipStream_t st);
-// a stack's attention arguments on the scratch s (kbs_rows: the K/V rows per sentence)
-AttnArgs attn_args(const Scratch& s, int B, int Sq, int Sk, long kbs_rows);
+// a stack's attention arguments on the scratch s (kbs_rows: the K/V rows per sentence; H heads
+// of 512 / H columns)
+AttnArgs attn_args(const Scratch& s, int B, int Sq, int Sk, long kbs_rows, int H);
 
 // ---- the fault decodes' parts the trials decode is built from (qtx_fault.hip) -------------
 int dfault_steps(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, int t0, int t1,

@@ -101,6 +101,7 @@ struct DecAttnArgs {
   // position): no read of *step, and only rows 0 .. position staged; 0: read *step and stage
   // all kv_bs rows (a step replayed at several positions)
   int host_step1;
+  int dk = 64;                // head width: 64, or 32 / 128 (k_dec_attn_hd, qtx_attn_heads.hip)
 };
 
 // Row quantizer / LayerNorm+quantizer over rows of D floats (one wave per row).
@@ -130,6 +131,8 @@ struct AttnArgs {
   const int* qpos_dev;                      // if set, query i's mask row = *qpos_dev + i
   int dec;                                  // a decoder layer's attention: the decoder's PV
                                             // order (oracle attention_pv dec)
+  int dk = 64;                              // head width (row width = H * dk): 64, or 32 / 128
+                                            // (qtx_attn_heads.hip)
 };
 
 // Fault in an attention MatMul of one (sentence b, head h) (k_attn_fault_rows): the
@@ -244,6 +247,9 @@ hipError_t launch_dec_attn(const DecAttnArgs& a, int B, hipStream_t st);
 // its kernel for 129 .. 512 rows to load (four waves per (sentence, head); a validated by
 // launch_dec_attn, which dispatches here)
 hipError_t launch_dec_attn_long(const DecAttnArgs& a, int B, hipStream_t st);
+// its kernel for head widths 32 and 128 (a.dk), 1 .. 512 rows to load (qtx_attn_heads.hip; a
+// validated by launch_dec_attn, which dispatches here)
+hipError_t launch_dec_attn_hd(const DecAttnArgs& a, int B, hipStream_t st);
 // [B * S, 512] int8 values (L layers, layer stride v_ls) -> k_dec_attn's 4-key group layout
 // (DecAttnArgs::vc; layer stride o_ls, B * ceil(S / 4) * 2048 bytes per layer)
 hipError_t launch_vgroup4(const int8_t* v, long v_ls, int L, int B, int S, int8_t* out,
@@ -412,8 +418,14 @@ hipError_t launch_attention_mfma(const AttnArgs& a, hipStream_t st);
 // the same attention for 129 .. 512 keys (k_attn_mfma_long, qtx_attn_long.hip);
 // hipErrorNotSupported outside that range and for the sk_dev / qpos_dev forms
 hipError_t launch_attention_mfma_long(const AttnArgs& a, hipStream_t st);
+// head widths 32 and 128 (a.dk; qtx_attn_heads.hip): k_attn_mfma_hd for host-known counts and
+// 1 .. 512 keys, k_attention_hd for the device-counter forms; hipErrorInvalidValue otherwise
+hipError_t launch_attention_mfma_hd(const AttnArgs& a, hipStream_t st);
+hipError_t launch_attention_valu_hd(const AttnArgs& a, hipStream_t st);
 // which kernel launch_attention runs for a (the values of include/qtx.h's QTX_ATTN_KERNEL_*)
-enum AttnKernel { ATTN_K_VALU = 0, ATTN_K_MFMA = 1, ATTN_K_MFMA_LONG = 2 };
+// (ATTN_K_*_HD: head widths 32 and 128, qtx_attn_heads.hip; no public value)
+enum AttnKernel { ATTN_K_VALU = 0, ATTN_K_MFMA = 1, ATTN_K_MFMA_LONG = 2, ATTN_K_VALU_HD = 3,
+                  ATTN_K_MFMA_HD = 4 };
 AttnKernel attention_kernel(const AttnArgs& a);
 // encoder self-attention, all heads of a sentence per workgroup, context quantized per
 // token -> ctx8 (row stride a.c_ld) + sctx; hipErrorNotSupported unless H == 8,

@@ -389,6 +389,8 @@ __global__ __launch_bounds__(256) void k_attention(AttnArgs a) {
 // reports its answer).  k_attention keeps the device-counter forms of the unfused decode step
 // (sk_dev / qpos_dev) and QTX_ATTN_VALU (QTX_DIAG build: timing experiments).
 AttnKernel attention_kernel(const AttnArgs& a) {
+  if (a.dk != 64)   // head widths 32 / 128 (qtx_attn_heads.hip)
+    return knobs().attn_valu || a.sk_dev || a.qpos_dev ? ATTN_K_VALU_HD : ATTN_K_MFMA_HD;
   if (knobs().attn_valu || a.sk_dev || a.qpos_dev || a.H * 64 > 4096) return ATTN_K_VALU;
   if (a.Sk <= 128) return ATTN_K_MFMA;
   return ATTN_K_MFMA_LONG;
@@ -397,7 +399,10 @@ AttnKernel attention_kernel(const AttnArgs& a) {
 hipError_t launch_attention(const AttnArgs& a, hipStream_t st) {
   if (a.B <= 0 || a.Sq <= 0) return hipSuccess;
   if (!a.sk_dev && (a.Sk <= 0 || a.Sk > ATT_MAXK)) return hipErrorInvalidValue;
+  if (a.dk != 32 && a.dk != 64 && a.dk != 128) return hipErrorInvalidValue;
   const AttnKernel kern = attention_kernel(a);
+  if (kern == ATTN_K_MFMA_HD) return launch_attention_mfma_hd(a, st);
+  if (kern == ATTN_K_VALU_HD) return launch_attention_valu_hd(a, st);
   if (kern != ATTN_K_VALU) {
     const hipError_t e = kern == ATTN_K_MFMA ? launch_attention_mfma(a, st) : launch_attention_mfma_long(a, st);
     if (e != hipErrorNotSupported) return e;

@@ -227,8 +227,8 @@ int norm_tensor_base(const qtx_config& c) { return 32 * c.n_layers; }
 
 int check_cfg(const qtx_config* c) {
   if (!c) return fail(QTX_E_INVALID, "null config");
-  if (c->d_model != 512 || c->n_heads * 64 != c->d_model)
-    return fail(QTX_E_UNSUPPORTED, "d_model must be 512 with 64-wide heads");
+  if (c->d_model != 512 || (c->n_heads != 4 && c->n_heads != 8 && c->n_heads != 16))
+    return fail(QTX_E_UNSUPPORTED, "d_model must be 512 with 4, 8 or 16 heads");
   if (c->d_ff % 256 || c->d_ff > 2048 || c->d_ff < 256)
     return fail(QTX_E_UNSUPPORTED, "d_ff must be a multiple of 256 <= 2048");
   if (c->weight_bits != 8 && c->weight_bits != 4)

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <mutex>
 
+#include "../../include/qtx_heads.h"
 #include "../../include/qtx_wide_vocab.h"
 #include "qtx_host.h"
 
@@ -374,6 +375,50 @@ int32_t qtx_attention_i8(const int8_t* q, const float* sq, const int8_t* k, cons
   if (Sk <= 0 || Sk > 512 || Sq <= 0) return fail(QTX_E_UNSUPPORTED, "Sk=%d (max 512)", Sk);
   const AttnArgs a = dense_attn_args(q, sq, k, sk, v, sv, mask, m_bs, m_is, B, H, Sq, Sk, ctx, dec);
   HIPCHK(launch_attention(a, (hipStream_t)stream));
+  return QTX_OK;
+}
+
+// ---- head widths 32 and 128 (include/qtx_heads.h) ----------------------------------------
+int32_t qtx_attention_heads_i8(const int8_t* q, const float* sq, const int8_t* k, const float* sk,
+                               const int8_t* v, const float* sv, const uint8_t* mask,
+                               int64_t m_bs, int64_t m_is, int32_t B, int32_t H, int32_t Sq,
+                               int32_t Sk, float* ctx, int32_t dec, int32_t dk, void* stream) {
+  if (dk == 64) return qtx_attention_i8(q, sq, k, sk, v, sv, mask, m_bs, m_is, B, H, Sq, Sk, ctx, dec, stream);
+  if (dk != 32 && dk != 128) return fail(QTX_E_INVALID, "dk=%d (32, 64 or 128)", dk);
+  if (!q || !sq || !k || !sk || !v || !sv || !ctx) return fail(QTX_E_INVALID, "null argument");
+  if (Sk <= 0 || Sk > 512 || Sq <= 0 || B < 0 || H <= 0 || H > 65535)
+    return fail(QTX_E_INVALID, "Sk=%d (1..512) Sq=%d B=%d H=%d", Sk, Sq, B, H);
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v))
+    return fail(QTX_E_INVALID, "q / k / v must be 16-byte aligned");
+  AttnArgs a = dense_attn_args(q, sq, k, sk, v, sv, mask, m_bs, m_is, B, H, Sq, Sk, ctx, dec);
+  const long D = (long)H * dk;   // (dense_attn_args lays out 64-wide heads)
+  a.q_bs = Sq * D; a.q_ld = D; a.k_bs = Sk * D; a.k_ld = D; a.v_bs = Sk * D; a.v_ld = D;
+  a.c_bs = Sq * D; a.c_ld = D; a.dk = dk;
+  HIPCHK(launch_attention(a, (hipStream_t)stream));
+  return QTX_OK;
+}
+
+int32_t qtx_decode_attention_heads(int32_t kv_new, const float* y, int64_t ldy, int8_t* kc,
+                                   int8_t* vc, float* skc, float* svc, int32_t kv_bs,
+                                   const int32_t* step_dev, int32_t S, const uint8_t* mask,
+                                   int32_t B, float* ctx, float* pmax, int32_t n_heads,
+                                   void* stream) {
+  if (n_heads == 8)
+    return qtx_decode_attention(kv_new, y, ldy, kc, vc, skc, svc, kv_bs, step_dev, S, mask, B, ctx, pmax, stream);
+  if (n_heads != 4 && n_heads != 16) return fail(QTX_E_INVALID, "n_heads=%d (4, 8 or 16)", n_heads);
+  if (!y || !kc || !vc || !skc || !svc || !ctx || !pmax)
+    return fail(QTX_E_INVALID, "null argument");
+  if (kv_new ? (!step_dev || kv_bs <= 0 || kv_bs > 512)
+             : (!mask || S <= 0 || S > 512 || S > kv_bs))
+    return fail(QTX_E_INVALID, "decode attention: bad step/mask/S/kv_bs");
+  if (!aligned16(y) || !aligned16(kc) || !aligned16(vc) || ldy % 4 || ldy < (kv_new ? 1536 : 512))
+    return fail(QTX_E_INVALID, "decode attention: y / kc / vc must be 16-byte aligned, "
+                               "ldy %% 4 == 0 and ldy >= the row width (ldy=%ld)", (long)ldy);
+  DecAttnArgs a{};
+  a.y = y; a.ldy = ldy; a.kc = kc; a.vc = vc; a.skc = skc; a.svc = svc; a.kv_bs = kv_bs;
+  a.step = step_dev; a.S = S; a.mask = mask; a.kv_new = kv_new;
+  a.ctx = ctx; a.pmax = pmax; a.B = B; a.dk = 512 / n_heads;
+  HIPCHK(launch_dec_attn(a, B, (hipStream_t)stream));
   return QTX_OK;
 }
 

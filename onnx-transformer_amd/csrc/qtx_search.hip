@@ -110,7 +110,10 @@ int32_t qtx_beam_decode(const qtx_model* m, const int64_t* src, const uint8_t* s
   // and the tail permutes that table, not the caches (beam 1 has nothing to permute and stays
   // on the plain kernels; up to 128 positions: k_dec_attn and the reorder, whatever S is).
   // The choice follows from max_len, beam and the switches, all in the step graphs' key.
-  const bool fused = greedy_fused_long(c, S, max_len);
+  // (k_dec_attn_beam is 64 columns wide: a model with 4 or 16 heads takes the unfused body
+  // where the 8-head one takes the ancestry path)
+  const bool fused = greedy_fused_long(c, S, max_len) &&
+                     !(c.n_heads != 8 && max_len > 128 && beam > 1 && !knobs().beam_reorder_long);
   w.tail.grouped = fused;
   w.tail.ancestry = fused && max_len > 128 && beam > 1 && !knobs().beam_reorder_long;
   w.g.beam = &w.tail;
@@ -267,6 +270,7 @@ int32_t qtx_score_targets(const qtx_model* m, const int64_t* src, const uint8_t*
                                    "below 2^30");
   if (n_faults > 0) {
     RC(check_fault_bits(c));
+    RC(check_fault_heads(c, true));
     if (K != 1) return fail(QTX_E_UNSUPPORTED, "fault trials need tgt_per_src == 1 (%d)", K);
     for (int n = 0; n < n_faults; ++n) {
       const qtx_fault* f = faults + n;

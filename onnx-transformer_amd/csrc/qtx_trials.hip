@@ -115,11 +115,11 @@ int kvtrials_step(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, in
     RC(ln_quant(s.x, B, L.ln[0], D, s.a8, s.sa, st));
     RC(lin(L.qkv, s.a8, s.sa, 0, nullptr, s.y, 3 * D, G_QKV));
     if (fused) {
-      HIPCHK(launch_dec_attn(dec_attn_self(g, l, B, max_len, t + 1), B, st));
+      HIPCHK(launch_dec_attn(dec_attn_self(g, l, B, max_len, t + 1, c.n_heads), B, st));
       for (const AttnFault& af : self_f) RC(fused_attn_fault(af, l, false));
     } else {
-      RC(cached_self_attn_unfused(g, l, B, max_len, t, nullptr, st));
-      AttnArgs a = attn_args(s, B, 1, t + 1, max_len);   // as cached_self_attn_unfused ran it
+      RC(cached_self_attn_unfused(g, l, B, max_len, t, nullptr, st, c.n_heads));
+      AttnArgs a = attn_args(s, B, 1, t + 1, max_len, c.n_heads);   // as cached_self_attn_unfused ran it
       a.k = g.kc[l]; a.sk = g.skc[l]; a.v = g.vc[l]; a.sv = g.svc[l];
       a.dec = 1;
       for (const AttnFault& af : self_f) HIPCHK(launch_attn_fault_rows(a, af, st));
@@ -129,11 +129,11 @@ int kvtrials_step(const qtx_model* m, GreedyWS& g, int B, int S, int max_len, in
     RC(ln_quant(s.x, B, L.ln[1], D, s.a8, s.sa, st));
     RC(lin(L.cq, s.a8, s.sa, 0, nullptr, s.y, D, G_CQ));
     if (fused) {
-      HIPCHK(launch_dec_attn(dec_attn_cross(g, l, B, S, g.mask), B, st));
+      HIPCHK(launch_dec_attn(dec_attn_cross(g, l, B, S, g.mask, c.n_heads), B, st));
       for (const AttnFault& af : cross_f) RC(fused_attn_fault(af, l, true));
     } else {                                             // cross_attn_block's attention
       RC(quant(s.y, D, B, D, s.q8, s.sq, st));
-      AttnArgs a = attn_args(s, B, 1, S, S);
+      AttnArgs a = attn_args(s, B, 1, S, S, c.n_heads);
       a.k = g.cross.k8[l]; a.sk = g.cross.sk[l]; a.v = g.cross.v8[l]; a.sv = g.cross.sv[l];
       a.mask = g.mask; a.m_bs = S; a.m_is = 0;
       a.dec = 1;
@@ -194,6 +194,7 @@ int32_t qtx_greedy_decode_kvtrials(const qtx_model* m, const int64_t* src, const
   RC(check_top2_vocab(c));
   const Groups gr = decode_groups(B);
   RC(check_workspace(ws_bytes, kvtrials_ws(c, gr, B, S, max_len)));
+  RC(check_fault_heads(c, true));
   const int last = max_len - 1;          // steps 0 .. last-1
   const bool fused = greedy_fused(c, S, max_len);
   // carved before the frame begins, as the kvfault decode: the upsets are validated against the

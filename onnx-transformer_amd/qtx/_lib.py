@@ -167,6 +167,13 @@ SIGNATURES_WIDE_VOCAB = {
     "qtx_decode_top2_wide": (I32, [P, P, I32, P, I64, P, P, P, P, P]),
 }
 
+# the same for include/qtx_heads.h (head widths 32 / 128: qtx_attention_i8 plus dk,
+# qtx_decode_attention plus n_heads)
+SIGNATURES_HEADS = {
+    "qtx_attention_heads_i8": (I32, [P, P, P, P, P, P, P, I64, I64, I32, I32, I32, I32, P, I32, I32, P]),
+    "qtx_decode_attention_heads": (I32, [I32, P, I64, P, P, P, P, I32, P, I32, P, I32, P, P, I32, P]),
+}
+
 
 def header_symbols(path=None) -> list[str]:
     """Function names declared in include/qtx.h (used by the ABI test)."""
@@ -187,7 +194,7 @@ def lib(build: bool = True):
         raise RuntimeError(f"libqtx.so missing at {path}; run __graft_entry__.build()")
     L = C.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **SIGNATURES_ENCTRIALS, **SIGNATURES_BEAM_LONG,
-                              **SIGNATURES_WIDE_VOCAB}.items():
+                              **SIGNATURES_WIDE_VOCAB, **SIGNATURES_HEADS}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     _lib = L

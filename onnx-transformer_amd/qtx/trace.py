@@ -84,6 +84,8 @@ def decoder_names(L: int, n_layers: int = 6) -> dict:
 class _Tracer:
     def __init__(self, model, rows_hint, weights):
         import torch
+        if model.cfg.n_heads != 8:   # k_attn_trace and the node names are 64 columns wide
+            raise NotImplementedError(f"the traced executor needs 8 heads (n_heads {model.cfg.n_heads})")
         self.torch, self.m, self.weights = torch, model, weights
         self.dev = model.device
         self.st = _stream(self.dev)
