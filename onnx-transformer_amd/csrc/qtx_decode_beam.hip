@@ -304,6 +304,7 @@ hipError_t launch_dec_attn_beam(const DecAttnArgs& a, const uint8_t* anc, int K,
       (a.host_step1 == 0 && !a.step) || (long)B * 512 >= (1L << 29))
     return hipErrorInvalidValue;
   if (K < 1 || K > BEAM_MAXK || B % K != 0) return hipErrorInvalidValue;
+  if (a.dk != 64) return launch_dec_attn_beam_hd(a, anc, K, B, st);   // head widths 32 / 128
   const KaLead l = da_lead<true>(a);
   const DaBeamTail t{{a.step, a.mask, a.ctx, a.pmax, a.B}, anc, K};
   k_dec_attn_beam<<<dim3(B, 8), dim3(256), 0, st>>>(QTX_KA_ARGS(l), t);

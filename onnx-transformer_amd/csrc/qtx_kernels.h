@@ -373,6 +373,9 @@ hipError_t launch_beam_reorder(int8_t* kc, int8_t* vc, float* skc, float* svc, i
 //   ancestry:      anc rows of slot j := its parent's over the step[0] valid positions, in place
 //   anc_init:      anc[b * K + k][j] = k
 hipError_t launch_dec_attn_beam(const DecAttnArgs& a, const uint8_t* anc, int K, int B, hipStream_t st);
+// its kernel for head widths 32 and 128 (a.dk; qtx_decode_beam_heads.hip; a validated by
+// launch_dec_attn_beam, which dispatches here; y and kc rows 16-byte aligned)
+hipError_t launch_dec_attn_beam_hd(const DecAttnArgs& a, const uint8_t* anc, int K, int B, hipStream_t st);
 hipError_t launch_beam_ancestry(uint8_t* anc, int B, int K, int max_len, const int* step,
                                 const int* parent, hipStream_t st);
 hipError_t launch_beam_anc_init(uint8_t* anc, int B, int K, int max_len, hipStream_t st);

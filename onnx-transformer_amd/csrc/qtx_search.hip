@@ -1,6 +1,7 @@
 // qtx_search.hip — the beam-search decode with EOS stop (qtx_beam_decode) and the
 // teacher-forced target scoring (qtx_score_targets) of the C-ABI (include/qtx.h), with their
-// per-op entries (the beam search past 128 positions: include/qtx_beam_long.h).  Both run the
+// per-op entries (the beam search past 128 positions: include/qtx_beam_long.h, and for 4 / 16
+// heads include/qtx_beam_heads.h).  Both run the
 // encoder once on the B sentences and replicate its cross K/V to their rows; the workspaces are
 // carved by qtx_carve.h.
 #include <hip/hip_runtime.h>
@@ -8,6 +9,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "../../include/qtx_beam_heads.h"
 #include "../../include/qtx_beam_long.h"
 #include "qtx_host.h"
 
@@ -109,11 +111,10 @@ int32_t qtx_beam_decode(const qtx_model* m, const int64_t* src, const uint8_t* s
   // Past 128 target positions the fused step reads the self caches through the ancestry table
   // and the tail permutes that table, not the caches (beam 1 has nothing to permute and stays
   // on the plain kernels; up to 128 positions: k_dec_attn and the reorder, whatever S is).
-  // The choice follows from max_len, beam and the switches, all in the step graphs' key.
-  // (k_dec_attn_beam is 64 columns wide: a model with 4 or 16 heads takes the unfused body
-  // where the 8-head one takes the ancestry path)
-  const bool fused = greedy_fused_long(c, S, max_len) &&
-                     !(c.n_heads != 8 && max_len > 128 && beam > 1 && !knobs().beam_reorder_long);
+  // The choice follows from max_len, beam and the switches, all in the step graphs' key, and
+  // not from the head count: the table is read by k_dec_attn_beam at 8 heads and by
+  // k_dec_attn_beam_hd (qtx_decode_beam_heads.hip) at 4 and 16.
+  const bool fused = greedy_fused_long(c, S, max_len);
   w.tail.grouped = fused;
   w.tail.ancestry = fused && max_len > 128 && beam > 1 && !knobs().beam_reorder_long;
   w.g.beam = &w.tail;
@@ -193,6 +194,29 @@ int32_t qtx_decode_attention_beam(const float* y, int64_t ldy, int8_t* kc, int8_
   DecAttnArgs a{};
   a.y = y; a.ldy = ldy; a.kc = kc; a.vc = vc; a.skc = skc; a.svc = svc; a.kv_bs = kv_bs;
   a.step = step_dev; a.kv_new = 1; a.ctx = ctx; a.pmax = pmax; a.B = B;
+  HIPCHK(launch_dec_attn_beam(a, anc, beam, B, (hipStream_t)stream));
+  return QTX_OK;
+}
+
+// ---- head widths 32 and 128 (include/qtx_beam_heads.h) -----------------------------------
+int32_t qtx_decode_attention_beam_heads(const float* y, int64_t ldy, int8_t* kc, int8_t* vc,
+                                        float* skc, float* svc, int32_t kv_bs,
+                                        const int32_t* step_dev, const uint8_t* anc, int32_t beam,
+                                        int32_t B, float* ctx, float* pmax, int32_t n_heads,
+                                        void* stream) {
+  if (n_heads == 8)
+    return qtx_decode_attention_beam(y, ldy, kc, vc, skc, svc, kv_bs, step_dev, anc, beam, B, ctx, pmax, stream);
+  if (n_heads != 4 && n_heads != 16) return fail(QTX_E_INVALID, "n_heads=%d (4, 8 or 16)", n_heads);
+  if (!y || !kc || !vc || !skc || !svc || !ctx || !pmax || !step_dev || !anc)
+    return fail(QTX_E_INVALID, "null argument");
+  if (kv_bs <= 0 || kv_bs > 512 || beam < 1 || beam > BEAM_MAXK || B < 0 || B % beam)
+    return fail(QTX_E_INVALID, "beam decode attention: kv_bs %d, beam %d, B %d", kv_bs, beam, B);
+  if (!aligned16(y) || !aligned16(kc) || !aligned16(vc) || ldy % 4 || ldy < 1536)
+    return fail(QTX_E_INVALID, "beam decode attention: y / kc / vc must be 16-byte aligned, "
+                               "ldy %% 4 == 0 and ldy >= 1536 (ldy=%ld)", (long)ldy);
+  DecAttnArgs a{};
+  a.y = y; a.ldy = ldy; a.kc = kc; a.vc = vc; a.skc = skc; a.svc = svc; a.kv_bs = kv_bs;
+  a.step = step_dev; a.kv_new = 1; a.ctx = ctx; a.pmax = pmax; a.B = B; a.dk = 512 / n_heads;
   HIPCHK(launch_dec_attn_beam(a, anc, beam, B, (hipStream_t)stream));
   return QTX_OK;
 }

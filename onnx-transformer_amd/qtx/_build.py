@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 REPO = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "libqtx.so")
-SOURCES = ["qtx_kernels.hip", "qtx_decode.hip", "qtx_decode_long.hip", "qtx_decode_beam.hip", "qtx_decode_wide.hip", "qtx_decode_dff.hip", "qtx_gemm.hip", "qtx_wsgemm.hip", "qtx_attn.hip",
+SOURCES = ["qtx_kernels.hip", "qtx_decode.hip", "qtx_decode_long.hip", "qtx_decode_beam.hip", "qtx_decode_beam_heads.hip", "qtx_decode_wide.hip", "qtx_decode_dff.hip", "qtx_gemm.hip", "qtx_wsgemm.hip", "qtx_attn.hip",
            "qtx_attn_long.hip", "qtx_attn_heads.hip",
            "qtx_ffn.hip", "qtx_model.hip", "qtx_api.hip", "qtx_fault.hip", "qtx_search.hip",
            "qtx_ops.hip", "qtx_knobs.hip", "qtx_rowfault.hip", "qtx_trials.hip", "qtx_enctrials.hip"]
@@ -38,6 +38,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 # error, and this kernel's contract is the oracle's bits — so new decode sources take scalar
 # fp32 ops only.  (qtx_decode.hip keeps its flags: its code object is the benchmark's.)
 # qtx_decode_beam.hip (that attention for beam rows, through the ancestry table): both, likewise.
+# qtx_decode_beam_heads.hip (the same for head widths 32 / 128): both, likewise.
 # qtx_decode_wide.hip (the step's tails above 8192 words): both, likewise.
 # qtx_decode_dff.hip (the step's FFN2 for d_ff = 256, 768 .. 1792): both, likewise.
 # qtx_attn_long.hip (attention past 128 keys): no packed fp32 instructions, for the same reason.
@@ -47,6 +48,7 @@ _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"qtx_decode.hip": _PRELOAD,
                 "qtx_decode_long.hip": _PRELOAD + _NO_PK_F32,
                 "qtx_decode_beam.hip": _PRELOAD + _NO_PK_F32,
+                "qtx_decode_beam_heads.hip": _PRELOAD + _NO_PK_F32,
                 "qtx_decode_wide.hip": _PRELOAD + _NO_PK_F32,
                 "qtx_decode_dff.hip": _PRELOAD + _NO_PK_F32,
                 "qtx_attn_long.hip": _NO_PK_F32,
@@ -73,6 +75,7 @@ def _inputs():
     files.append(os.path.join(REPO, "include", "qtx_beam_long.h"))
     files.append(os.path.join(REPO, "include", "qtx_wide_vocab.h"))
     files.append(os.path.join(REPO, "include", "qtx_heads.h"))
+    files.append(os.path.join(REPO, "include", "qtx_beam_heads.h"))
     files.append(os.path.abspath(__file__))
     return files
 

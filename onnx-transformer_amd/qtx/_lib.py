@@ -174,6 +174,11 @@ SIGNATURES_HEADS = {
     "qtx_decode_attention_heads": (I32, [I32, P, I64, P, P, P, P, I32, P, I32, P, I32, P, P, I32, P]),
 }
 
+# the same for include/qtx_beam_heads.h (qtx_decode_attention_beam plus n_heads)
+SIGNATURES_BEAM_HEADS = {
+    "qtx_decode_attention_beam_heads": (I32, [P, I64, P, P, P, P, I32, P, P, I32, I32, P, P, I32, P]),
+}
+
 
 def header_symbols(path=None) -> list[str]:
     """Function names declared in include/qtx.h (used by the ABI test)."""
@@ -194,7 +199,8 @@ def lib(build: bool = True):
         raise RuntimeError(f"libqtx.so missing at {path}; run __graft_entry__.build()")
     L = C.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **SIGNATURES_ENCTRIALS, **SIGNATURES_BEAM_LONG,
-                              **SIGNATURES_WIDE_VOCAB, **SIGNATURES_HEADS}.items():
+                              **SIGNATURES_WIDE_VOCAB, **SIGNATURES_HEADS,
+                              **SIGNATURES_BEAM_HEADS}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     _lib = L

@@ -22,6 +22,15 @@ two beam kernels (profiles/beam_ab.md).  Not wired into bench.py.
         what one step pays either way at 130 and 500 cached positions of max_len 512 (128 rows,
         6 layers), us per launch in a captured graph: k_beam_reorder against k_beam_ancestry,
         k_dec_attn_long against k_dec_attn_beam (one-slot and all-mixed tables).
+    python tools/beam_ab.py heads --heads 4|16 [--lib PATH] [--rounds 5]
+        the beam decode past 128 keys of a 4- / 16-head model (profiles/beam_heads_ab.md): the
+        default model's shape with n_heads set and a 512-row positional table, B = 4 and 32,
+        beam = 4, early_exit off, S = 72, max_len = 140 and 512.  --lib: the parent commit's
+        build (these shapes on the unfused body), or the diagnostic build with
+        QTX_BEAM_REORDER_LONG=1 (the fused step on k_dec_attn_hd, caches reordered).
+    python tools/beam_ab.py heads-kernels
+        k_dec_attn_hd against k_dec_attn_beam_hd (one-slot and all-mixed tables) at 130 and 500
+        cached positions, 128 rows, us per launch in a captured graph, for both head counts.
 """
 import argparse
 import ctypes as C
@@ -120,6 +129,40 @@ def long_decode(args):
               f"max {max(v):9.3f}  ({med * 1e3 / (L - 1):7.1f} us/step, {len(v)} rounds)", flush=True)
 
 
+def heads_decode(args):
+    import torch
+    if args.lib:
+        os.environ["QTX_LIB_PATH"] = args.lib
+        from qtx import _lib
+        old = C.CDLL(args.lib)
+        for t in ("SIGNATURES", "SIGNATURES_BEAM_HEADS"):
+            setattr(_lib, t, {k: v for k, v in getattr(_lib, t).items() if hasattr(old, k)})
+    from qtx.model import QtxModel, to_u8_mask
+    from qtx.weights import ModelConfig, synthetic_state_dict
+    cfg = ModelConfig(n_heads=args.heads, max_len=512)
+    model = QtxModel(synthetic_state_dict(20241223, cfg), cfg)
+    rng = np.random.default_rng(11)
+    dev, S = model.device, 72
+    cases = {}
+    for B in (4, 32):
+        src = make_src(rng, B, S)
+        s = torch.from_numpy(src).to(dev)
+        m = to_u8_mask((src != 2)[:, None, :], dev).reshape(B, S)
+        for L in (140, 512):
+            cases[(B, L)] = lambda s=s, m=m, L=L: model.beam(s, m, max_len=L, beam_size=4, early_exit=False)
+    for fn in cases.values():          # warm-up: graph capture, workspace growth
+        for _ in range(2):
+            fn()
+    times = {k: [] for k in cases}
+    for _ in range(args.rounds):       # alternating rounds
+        for k, fn in cases.items():
+            times[k].append(timed(fn, torch))
+    for (B, L), v in times.items():
+        med = statistics.median(v)
+        print(f"beam H={args.heads:2d} B={B:2d} beam=4 S={S} max_len={L:3d} median {med:9.3f} ms  min {min(v):9.3f}  "
+              f"max {max(v):9.3f}  ({med * 1e3 / (L - 1):7.1f} us/step, {len(v)} rounds)", flush=True)
+
+
 def graph_us(torch, fn, N=50):
     """us per launch of fn(stream), N back-to-back launches in one captured graph, 10 replays."""
     g, s = torch.cuda.CUDAGraph(), torch.cuda.Stream()
@@ -183,6 +226,38 @@ def long_kernels(args):
             print(f"{pos:3d} positions  k_dec_attn_beam (one layer, {name:9s})      {us:8.2f} us", flush=True)
 
 
+def heads_kernels(args):
+    import torch
+    from qtx import _lib
+    lib = _lib.lib(build=False)
+    B, K, ML = 32, 4, 512
+    R, G4 = B * K, ML // 4
+    P = lambda t: C.c_void_p(t.data_ptr())
+    rng = np.random.default_rng(0)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    kc = torch.randint(-127, 128, (R, ML * 512), dtype=torch.int8, device="cuda")
+    vc = torch.randint(-127, 128, (R, G4 * 2048), dtype=torch.int8, device="cuda")
+    skc = torch.full((R, ML), 0.01, dtype=torch.float32, device="cuda")
+    svc = torch.full((R, ML), 0.01, dtype=torch.float32, device="cuda")
+    y = T(rng.standard_normal((R, 1536)).astype(np.float32))
+    ctx = torch.zeros((R, 512), dtype=torch.float32, device="cuda")
+    pm = torch.zeros((8, R), dtype=torch.float32, device="cuda")
+    slot, j = np.arange(K)[:, None], np.arange(ML)[None, :]
+    tables = {"one slot": np.tile(np.broadcast_to(slot, (K, ML)), (B, 1)),
+              "all mixed": np.tile((slot + j) % K, (B, 1))}
+    for H in (4, 16):
+        for pos in (130, 500):         # cached positions; the step's own position is pos
+            step = T(np.array([pos, 0, 0, 0], np.int32))
+            us = graph_us(torch, lambda st: lib.qtx_decode_attention_heads(
+                1, P(y), 1536, P(kc), P(vc), P(skc), P(svc), ML, P(step), 0, None, R, P(ctx), P(pm), H, st))
+            print(f"H={H:2d} {pos:3d} positions  k_dec_attn_hd                      {us:8.2f} us", flush=True)
+            for name, t in tables.items():
+                anc = T(t.astype(np.uint8))
+                us = graph_us(torch, lambda st: lib.qtx_decode_attention_beam_heads(
+                    P(y), 1536, P(kc), P(vc), P(skc), P(svc), ML, P(step), P(anc), K, R, P(ctx), P(pm), H, st))
+                print(f"H={H:2d} {pos:3d} positions  k_dec_attn_beam_hd ({name:9s})     {us:8.2f} us", flush=True)
+
+
 def kernels(args):
     import torch
     from qtx import _lib
@@ -229,10 +304,12 @@ def kernels(args):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["decode", "kernels", "long", "long-kernels"])
+    ap.add_argument("what", choices=["decode", "kernels", "long", "long-kernels", "heads", "heads-kernels"])
     ap.add_argument("--lib", default=None)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--heads", type=int, default=4, choices=[4, 16])
     ap.add_argument("--no-beam", action="store_true",
                     help="decode: the greedy lines only (this build against --lib, like for like)")
     a = ap.parse_args()
-    {"decode": decode, "kernels": kernels, "long": long_decode, "long-kernels": long_kernels}[a.what](a)
+    {"decode": decode, "kernels": kernels, "long": long_decode, "long-kernels": long_kernels,
+     "heads": heads_decode, "heads-kernels": heads_kernels}[a.what](a)
